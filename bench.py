@@ -2,6 +2,12 @@
 """bench.py -- series-elements/s and % HBM roofline of the fused fill + ACF hot path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5|c1|ewma_fit]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy.
+--full adds the legs that take runs of their own: the CPU baseline sample (with its check
+of the GPU results against the oracle) and, for stage_c2, the host-resident staging leg.
 
 Default workload (the BASELINE.json metric "fill+lag+ACF", config C3): every rank owns
 a C3 shard of 12,500 series x 982,800 minute bars (fp64, 5 % NaN, Philox synthetic,
@@ -82,6 +88,14 @@ def parse():
     ap.add_argument("--series", type=int, default=0, help="override series per GPU (testing)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: the CPU baseline sample and its check "
+                         "(see --cpu-seconds / --no-cpu-baseline) and stage_c2's host-resident staging leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step computed to DIR/<name>.npy "
+                         "(float64; arrays over %d MB as a fixed seeded sample of their elements; NaN / inf "
+                         "positions as 0 there and coded in DIR/<name>_nonfinite.npy)"
+                         % (DUMP_WHOLE_BYTES >> 20))
     ap.add_argument("--percall", action="store_true",
                     help="per-call latency of S = 1 (per-series) calls against the one-core CPU loop: the "
                          "crossover INTEGRATION.md's JVM facade uses (prints its own JSON line, not the metric)")
@@ -242,6 +256,31 @@ def main():
     elems = float(S) * T * world * args.steps
     value = elems / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after the last timed step (rank 0's shard; the
+        # gathered block where the step gathers one)
+        if args.workload in ("c3", "c1", "c1_rule3", "c3_rule3"):
+            got = {"filled": out, "acf": acf if fill_acf.gathered is None else fill_acf.gathered, "err": err}
+        elif args.workload in ("c2", "stage_c2", "spline"):
+            got = {"out": out, "err": err}
+        elif args.workload == "c5":
+            got = {"filled": out, "lag_matrix_last_batch": lagbuf[:S - (S - 1) // LB * LB], "err": err}
+        elif args.workload == "stats":
+            got = {"stats": stats}
+        elif args.workload == "nan_instants":
+            got = {"flags": flags, "active": active[:n_keep], "kept": out.view(-1)[:S * n_keep].view(S, n_keep)}
+        elif args.workload == "wire_decode":
+            got = {"out": out}
+        elif args.workload == "to_instants":
+            got = {"instants": inst}
+        elif args.workload == "garch_fit":
+            got = {"params": gpar, "err": err}
+        elif args.workload == "ewma_fit":
+            got = {"smoothing": smooth, "err": err}
+        else:
+            got = {"residuals": out, "c": c_fit, "coefficients": coef_fit, "err": err}
+        dump_outputs(args.dump_outputs, got)
     # dominant kernel (one launch per step, or one per lag-matrix batch for c5), timed with
     # HIP events the library records on the launch stream (sts_profile_begin/end)
     bytes_per_step = 16.0 * S * T        # 8 B read + 8 B written per element
@@ -276,7 +315,9 @@ def main():
                            "sts::garch_tail_kernel<64> (wave per series past 64 passes)",
               "ewma_fit": "sts::ewma_fit_kernel<32,64> (lane-per-series commons-math3 optimizer; one sse+gradient "
                           "pass over the wave's series block per optimizer request)"}[args.workload]
-    staging = staging_leg(args, lib, x, out, smooth, S, T) if args.workload == "stage_c2" and rank == 0 else None
+    staging = None
+    if args.full and args.workload == "stage_c2" and rank == 0:
+        staging = staging_leg(args, lib, x, out, smooth, S, T)
     roofline = None
     if launches[0] > 0:
         avg_ms = kern_ms[0] / launches[0]
@@ -292,7 +333,7 @@ def main():
             roofline["fp64"] = fp
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload != "stage_c2":   # the CPU leg is an N = 1 report
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload != "stage_c2":   # the CPU leg is an N = 1 report
         cpu = cpu_baseline(args, S, T, K, seed, nan_p, out, acf, p_ar, smooth,
                            gpar if args.workload == "garch_fit" else None,
                            (c_fit, coef_fit) if args.workload in ("c4", "c4_levels") else None)
@@ -385,6 +426,42 @@ def emit(line, rank):
     """Rank 0 prints the line; every other rank prints nothing."""
     if rank == 0:
         print(json.dumps(line), flush=True)
+
+
+DUMP_WHOLE_BYTES = 16 << 20     # arrays up to this size (as float64) are written whole
+DUMP_SAMPLE_ELEMS = 2 << 20     # larger ones as this many elements (16 MB of float64)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path, tensors):
+    """--dump-outputs: every array as path/<name>.npy in float64.  An array over
+    DUMP_WHOLE_BYTES is written as DUMP_SAMPLE_ELEMS of its elements (row-major flat indices
+    drawn once from a CPU generator seeded with DUMP_SEED and the array's size, in increasing
+    order: the same elements in every run of the same arguments).  An array with NaN or
+    infinite values comes as two finite files, the values and <name>_nonfinite.npy (below).
+    At most four arrays per workload, so a dump stays under 64 MB."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in tensors.items():
+        flat = t.reshape(-1)
+        if flat.numel() * 8 > DUMP_WHOLE_BYTES:
+            g = torch.Generator(device="cpu")
+            g.manual_seed(DUMP_SEED + flat.numel())
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE_ELEMS,), generator=g, dtype=torch.int64).sort().values
+            arr = flat[idx.to(flat.device)].to(torch.float64).cpu().numpy()
+        else:
+            arr = t.to(torch.float64).cpu().numpy()
+        # NaN is a value of this API (fill("linear") leaves the NaNs before the first and after
+        # the last observation, and the ACF of such a series is NaN), but a file of finite numbers
+        # compares element for element.  So the non-finite positions go into <name>_nonfinite.npy
+        # (0 finite, 1 NaN, 2 +inf, 3 -inf; float32, written only when there is one) and hold 0 in
+        # <name>.npy: the two files together are the array, and every file is finite.
+        code = np.isnan(arr) * 1 + np.isposinf(arr) * 2 + np.isneginf(arr) * 3
+        if code.any():
+            arr = np.where(code != 0, 0.0, arr)
+            np.save(os.path.join(path, name + "_nonfinite.npy"), code.astype(np.float32))
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def staging_leg(args, lib, x, out, smooth, S, T):

@@ -19,6 +19,7 @@
 Every build uses -fno-sanitize-recover=all, so any report fails the run.
 """
 import os
+import platform
 import shutil
 import subprocess
 
@@ -116,12 +117,26 @@ TSAN = ["-fsanitize=thread", "-g", "-O1"]
 TSAN_ENV = dict(os.environ, TSAN_OPTIONS="halt_on_error=1:second_deadlock_stack=1")
 
 
+def no_aslr():
+    """Command prefix that starts a program with address-space randomisation off for that one
+    process (setarch -R), or [] where the kernel does not allow it.  The ThreadSanitizer runtime
+    refuses to start ("FATAL: ThreadSanitizer: unexpected memory mapping", exit 66, before main)
+    when the kernel places the executable or its libraries outside the ranges its shadow layout
+    expects, which hosts with vm.mmap_rnd_bits = 32 do most of the time."""
+    setarch = shutil.which("setarch")
+    if setarch is not None:
+        pre = [setarch, platform.machine(), "-R"]
+        if subprocess.run([*pre, "true"], capture_output=True).returncode == 0:
+            return pre
+    return []
+
+
 def test_stage_pool_under_tsan(tmp_path):
     gxx = need("g++")
     exe = str(tmp_path / "stage_pool_tsan")
     subprocess.check_call([gxx, *TSAN, "-std=c++17", "-I", CSRC, os.path.join(NATIVE, "stage_pool_tsan.cpp"),
                            "-o", exe, "-pthread"])
-    r = subprocess.run([exe, "16", "400"], capture_output=True, text=True, env=TSAN_ENV, timeout=600)
+    r = subprocess.run([*no_aslr(), exe, "16", "400"], capture_output=True, text=True, env=TSAN_ENV, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().startswith("ok"), r.stdout[-3000:] + r.stderr[-6000:]
     assert "WARNING: ThreadSanitizer" not in r.stderr, r.stderr[-6000:]
 
@@ -144,6 +159,6 @@ def test_host_entry_points_concurrent_under_tsan(tmp_path):
     subprocess.check_call([hipcc, "-fsanitize=thread", "-fno-gpu-sanitize", "--offload-arch=gfx950",
                            *objs, *dev_objs, "-o", exe, "-pthread"])
     env = dict(TSAN_ENV, HIP_VISIBLE_DEVICES="")
-    r = subprocess.run([exe, "8"], capture_output=True, text=True, env=env, timeout=600)
+    r = subprocess.run([*no_aslr(), exe, "8"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-3000:] + r.stderr[-6000:]
     assert "WARNING: ThreadSanitizer" not in r.stderr, r.stderr[-6000:]

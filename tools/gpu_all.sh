@@ -16,7 +16,7 @@ step() {  # step <name> <seconds> <cmd...>
 }
 for s in ${STEPS:-c1 c2 c4 c5 prof fetch write}; do
   case $s in
-    c1|c2|c3|c4|c5|stage_c2|ewma_fit|garch_fit|stats|nan_instants|to_instants|wire_decode) step bench_$s 300 python -u bench.py --workload $s ;;
+    c1|c2|c3|c4|c5|stage_c2|ewma_fit|garch_fit|stats|nan_instants|to_instants|wire_decode) step bench_$s 300 python -u bench.py --workload $s --full ;;
     prof) step prof_c3 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_c3 -o bench --output-format csv -- python -u bench.py ;;
     prof_*) W=${s#prof_}; step prof_$W 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$W -o bench --output-format csv -- python -u bench.py --workload $W --no-cpu-baseline ;;
     fetch) step pmc_fetch_c3 300 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch_c3 -o bench --output-format csv -- python -u bench.py --steps 2 --warmup 0 --no-cpu-baseline ;;

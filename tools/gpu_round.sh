@@ -17,8 +17,8 @@ STEPS=${STEPS:-"tests bench smoke"}
 for s in $STEPS; do
   case $s in
     tests) run pytest_gpu 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread -p no:cacheprovider ;;
-    bench) run bench_small 400 python -u bench.py --series ${BENCH_SERIES:-1000} --steps 3 --warmup 1 --cpu-seconds 3 ;;
-    benchfull) run bench_full 600 python -u bench.py ;;
+    bench) run bench_small 400 python -u bench.py --series ${BENCH_SERIES:-1000} --steps 3 --warmup 1 --full --cpu-seconds 3 ;;
+    benchfull) run bench_full 600 python -u bench.py --full ;;
     smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
     prof) export TMPDIR=/tmp; run rocprof_stats 600 rocprofv3 --kernel-trace --stats -T -d gpurun_out/prof -o bench --output-format csv -- python -u bench.py --series ${PROF_SERIES:-2000} --steps 5 --warmup 1 --no-cpu-baseline ;;
     pmcfetch) export TMPDIR=/tmp; run pmc_fetch 300 rocprofv3 --pmc FETCH_SIZE -T -d gpurun_out/pmc_fetch -o bench --output-format csv -- python -u bench.py --series ${PROF_SERIES:-2000} --steps 2 --warmup 0 --no-cpu-baseline ;;

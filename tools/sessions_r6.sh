@@ -30,7 +30,7 @@ case "$SESSION" in
     timeout -k 10 900 $PYT tests/test_parity_gpu.py -k "acf or autocorr or rule3 or short or constant" > $O/rule3_pytest2.log 2>&1 || { tail -40 $O/rule3_pytest2.log; exit 1; }
     tail -2 $O/rule3_pytest2.log
     for w in c1_rule3 c3_rule3 c1; do
-      timeout -k 10 300 python -u bench.py --workload $w --steps 10 --warmup 3 --cpu-seconds 4 > $O/bench_$w.json 2> $O/bench_$w.err || { tail -20 $O/bench_$w.err; exit 1; }
+      timeout -k 10 300 python -u bench.py --workload $w --steps 10 --warmup 3 --full --cpu-seconds 4 > $O/bench_$w.json 2> $O/bench_$w.err || { tail -20 $O/bench_$w.err; exit 1; }
       python -c "import json,sys; d=json.load(open('$O/bench_$w.json')); r=d['roofline']; print('$w', round(d['ms_per_step'],3), r['avg_kernel_ms'], r['frac'], d['cpu_baseline']['sample_check'])"
     done
     ;;
@@ -50,7 +50,7 @@ case "$SESSION" in
           res16) E="STS_HIP_LIB=$AB STS_EWMA_RES=16" ;;
           res32) E="STS_HIP_LIB=$AB STS_EWMA_RES=32" ;;
         esac
-        env $E timeout -k 10 300 python -u bench.py --workload ewma_fit --steps 3 --warmup 1 --cpu-seconds 2 > $O/ewmares_$V.json 2> $O/ewmares_$V.err || { tail -20 $O/ewmares_$V.err; exit 1; }
+        env $E timeout -k 10 300 python -u bench.py --workload ewma_fit --steps 3 --warmup 1 --full --cpu-seconds 2 > $O/ewmares_$V.json 2> $O/ewmares_$V.err || { tail -20 $O/ewmares_$V.err; exit 1; }
         python -c "import json; d=json.load(open('$O/ewmares_$V.json')); r=d['roofline']; print(json.dumps({'variant': '$V', 'rep': $rep, 'kernel_ms': r['avg_kernel_ms'], 'ms_per_step': d['ms_per_step'], 'check': d['cpu_baseline']['sample_check']}))" | tee -a $O/ewmares.jsonl
       done
     done
@@ -66,7 +66,7 @@ case "$SESSION" in
     for rep in 1 2 3; do
       for L in skip norefskip; do
         if [ $L = norefskip ]; then E="STS_HIP_LIB=$V"; else E=""; fi
-        env $E timeout -k 10 200 python -u bench.py --workload c4 --steps 20 --warmup 5 --cpu-seconds 2 > $O/arskip_$L.json 2>/dev/null || exit 1
+        env $E timeout -k 10 200 python -u bench.py --workload c4 --steps 20 --warmup 5 --full --cpu-seconds 2 > $O/arskip_$L.json 2>/dev/null || exit 1
         python -c "import json; d=json.load(open('$O/arskip_$L.json')); r=d['roofline']; print(json.dumps({'lib': '$L', 'rep': $rep, 'kernel_ms': r['avg_kernel_ms'], 'frac': r['frac'], 'check': d['cpu_baseline']['sample_check']}))" | tee -a $O/arskip.jsonl
       done
     done
@@ -86,7 +86,7 @@ case "$SESSION" in
         L=$AB; PP=$P
         case $P in 0|1) ;; *) L=spark-timeseries_amd/build/var_$P/libsts_hip.so; PP=1 ;; esac
         for w in c1 ${PAIR_WL-c1_rule3}; do
-          STS_SHORT_PAIR=$PP STS_HIP_LIB=$L timeout -k 10 200 python -u bench.py --workload $w --steps 20 --warmup 5 --cpu-seconds 2 > $O/pair_${w}_$P.json 2>/dev/null || exit 1
+          STS_SHORT_PAIR=$PP STS_HIP_LIB=$L timeout -k 10 200 python -u bench.py --workload $w --steps 20 --warmup 5 --full --cpu-seconds 2 > $O/pair_${w}_$P.json 2>/dev/null || exit 1
           python -c "import json; d=json.load(open('$O/pair_${w}_$P.json')); r=d['roofline']; print(json.dumps({'workload': '$w', 'form': '$P', 'rep': $rep, 'kernel_ms': r['avg_kernel_ms'], 'frac': r['frac'], 'ms_per_step': d['ms_per_step'], 'check': d['cpu_baseline']['sample_check']}))" | tee -a $O/pair.jsonl
         done
       done
@@ -118,7 +118,7 @@ case "$SESSION" in
     for rep in 1 2 3; do
       for L in trim notrim; do
         if [ $L = notrim ]; then E="STS_HIP_LIB=$V"; else E=""; fi
-        env $E timeout -k 10 200 python -u bench.py --workload c1 --steps 20 --warmup 5 --cpu-seconds 2 > $O/trim_$L.json 2>/dev/null || exit 1
+        env $E timeout -k 10 200 python -u bench.py --workload c1 --steps 20 --warmup 5 --full --cpu-seconds 2 > $O/trim_$L.json 2>/dev/null || exit 1
         python -c "import json; d=json.load(open('$O/trim_$L.json')); r=d['roofline']; print(json.dumps({'lib': '$L', 'rep': $rep, 'kernel_ms': r['avg_kernel_ms'], 'frac': r['frac'], 'check': d['cpu_baseline']['sample_check']}))" | tee -a $O/trim.jsonl
       done
     done
@@ -132,7 +132,7 @@ case "$SESSION" in
       for w in ${DPP_WL:-c1 c2 c4}; do
         for L in new ${DPP_LIBS:-head}; do
           if [ $L = new ]; then E=""; else E="STS_HIP_LIB=spark-timeseries_amd/build/var_$L/libsts_hip.so"; fi
-          env $E timeout -k 10 200 python -u bench.py --workload $w --steps 20 --warmup 5 --cpu-seconds 2 > $O/dpp_${w}_$L.json 2>/dev/null || exit 1
+          env $E timeout -k 10 200 python -u bench.py --workload $w --steps 20 --warmup 5 --full --cpu-seconds 2 > $O/dpp_${w}_$L.json 2>/dev/null || exit 1
           python -c "import json; d=json.load(open('$O/dpp_${w}_$L.json')); r=d['roofline']; print(json.dumps({'workload': '$w', 'lib': '$L', 'rep': $rep, 'kernel_ms': r['avg_kernel_ms'], 'frac': r['frac'], 'check': d['cpu_baseline']['sample_check']}))" | tee -a $O/dpp.jsonl
         done
       done
@@ -147,7 +147,7 @@ case "$SESSION" in
     for rep in 1 2 3; do
       for L in lds old; do
         if [ $L = old ]; then E="STS_HIP_LIB=$V"; else E=""; fi
-        env $E timeout -k 10 300 python -u bench.py --workload spline --steps 5 --warmup 2 --cpu-seconds 2 > $O/splds_$L.json 2>/dev/null || exit 1
+        env $E timeout -k 10 300 python -u bench.py --workload spline --steps 5 --warmup 2 --full --cpu-seconds 2 > $O/splds_$L.json 2>/dev/null || exit 1
         python -c "import json; d=json.load(open('$O/splds_$L.json')); r=d['roofline']; print(json.dumps({'lib': '$L', 'rep': $rep, 'ms_per_step': d['ms_per_step'], 'kernel_ms': r['avg_kernel_ms'], 'frac': r['frac'], 'check': d['cpu_baseline']['sample_check']}))" | tee -a $O/splds.jsonl
       done
     done
@@ -204,7 +204,7 @@ PY
     for rep in 1 2 3; do
       for L in prod ew6432; do
         if [ $L = prod ]; then E=""; else E="STS_HIP_LIB=$V"; fi
-        env $E timeout -k 10 200 python -u bench.py --workload ewma_fit --steps 5 --warmup 2 --cpu-seconds 2 > $O/ew_$L.json 2>/dev/null || exit 1
+        env $E timeout -k 10 200 python -u bench.py --workload ewma_fit --steps 5 --warmup 2 --full --cpu-seconds 2 > $O/ew_$L.json 2>/dev/null || exit 1
         python -c "import json; d=json.load(open('$O/ew_$L.json')); r=d['roofline']; print(json.dumps({'lib': '$L', 'rep': $rep, 'kernel_ms': r['avg_kernel_ms'], 'check': d['cpu_baseline']['sample_check']}))" | tee -a $O/ew.jsonl
       done
     done
@@ -227,7 +227,7 @@ PY
     for rep in 1 2 3; do
       for L in prod compact; do
         if [ $L = prod ]; then E=""; else E="STS_HIP_LIB=$V"; fi
-        env $E timeout -k 10 200 python -u bench.py --workload c1 --steps 20 --warmup 5 --cpu-seconds 2 > $O/compact_$L.json 2>/dev/null || exit 1
+        env $E timeout -k 10 200 python -u bench.py --workload c1 --steps 20 --warmup 5 --full --cpu-seconds 2 > $O/compact_$L.json 2>/dev/null || exit 1
         python -c "import json; d=json.load(open('$O/compact_$L.json')); r=d['roofline']; print(json.dumps({'lib': '$L', 'rep': $rep, 'kernel_ms': r['avg_kernel_ms'], 'frac': r['frac'], 'check': d['cpu_baseline']['sample_check']}))" | tee -a $O/compact.jsonl
       done
     done
