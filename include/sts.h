@@ -16,6 +16,23 @@
  * TimeSeriesRDD.collectAsTimeSeries (S/TimeSeriesRDD.scala:66-71) and each
  * record's DenseVector.data.  NaN marks a missing observation.
  *
+ * Panel layout contract (every entry point that takes a panel, `_host` variants included;
+ * pinned by tests/test_layout_gpu.py on padded, odd-strided and skewed panels whose padding
+ * holds NaN or a finite sentinel):
+ *   - Results depend only on the elements (s, t < T).  Whatever sits in a row's padding
+ *     (t in [T, ld)), before the first row or after the last never reaches a result, an
+ *     error code or a flag.
+ *   - No entry point writes an output element outside (s, t < T); for a lag matrix, a
+ *     transpose, a gathered panel or a per-series array that is: outside the documented
+ *     output block.  The padding is the caller's and keeps its bits.
+ *   - No entry point writes to an input (in place calls, out == in, write (s, t < T) only).
+ *   - Reads may touch only the 128-byte lines that hold panel elements (see
+ *     sts_series_stats below): up to 15 doubles before in[0] and after the last element,
+ *     never a line the panel does not touch.
+ *   - Any 8-byte-aligned base and any ld >= T are accepted.  A 16-byte-aligned base with
+ *     even ld (and, for some kernels, even T) only selects faster load / store forms; the
+ *     result is held to the same bar in every layout.
+ *
  * Memory: functions without a `_host` suffix take DEVICE pointers (HBM,
  * e.g. hipMalloc'd) and are stream-ordered on `stream` (a hipStream_t; NULL
  * means hipStreamPerThread, so concurrent executor threads never serialise
