@@ -327,6 +327,57 @@ int sts_ar_fit_remove(const double* in, double* out, int64_t S, int64_t T, int64
                       int64_t ld_out, int p, int no_intercept, double* c, double* coef,
                       int32_t* err_per_series, void* stream);
 
+/* ---- t1-t4: TimeSeriesStatisticalTests (S/stats/TimeSeriesStatisticalTests.scala), one scalar
+ * statistic per series of a panel.  stat (and pvalue, which may be NULL) are device arrays of S
+ * doubles; the input is never written; stream-ordered.  A series holding any NaN gets a NaN
+ * statistic (and p-value) with status 0.  bgtest / bptest take a per-series factor matrix and
+ * are not part of this ABI. */
+typedef enum sts_regression {
+    STS_REG_NC = 0,   /* no constant                 */
+    STS_REG_C = 1,    /* constant                    */
+    STS_REG_CT = 2,   /* constant + trend            */
+    STS_REG_CTT = 3   /* constant + trend + trend^2  */
+} sts_regression;
+/* "nc" / "c" / "ct" / "ctt" -> sts_regression; -2 for anything else (addTrend's
+ * IllegalArgumentException, :177). */
+int sts_regression_from_name(const char* name);
+
+/* t1: adftest(ts, maxLag, regression) (:204-232).  nObs = T - 1 - maxLag rows; response
+ * diff[T-1-nObs .. T-1); regressors ts[T-nObs-1 .. T-1), the lag 1..maxLag columns of
+ * lagMatTrimBoth(diff, maxLag, true) (S/Lag.scala:62-77), then addTrend's columns 1, r, r^2 with
+ * r = 1..nObs (:171-192); OLS without intercept; stat = beta_0 / se(beta_0), se^2 = RSS /
+ * (nObs - k) * [(X'X)^-1]_00.  Computed as the Frisch-Waugh two-pass form (every column detrended
+ * on orthogonal polynomials, then the lags taken out of the level and the response through a
+ * Cholesky factor of the lags' Gram matrix): 1e-10 relative to exact
+ * arithmetic on well-posed series, where the reference's Householder QR itself is up to ~5e-10
+ * off on trending series.  0 <= maxLag <= 31; a regression outside sts_regression ->
+ * STS_ERR_BAD_ARG.  nObs <= k -> STS_ERR_NOT_ENOUGH_DATA (parity note: the reference throws for
+ * nObs < k only and returns a non-finite value at nObs == k).  Per series: an exactly singular
+ * design (a constant series with maxLag >= 1) -> STS_ERR_SINGULAR and a NaN statistic.
+ * pvalue: mackinnonp (:141-156), MacKinnon (1994), N = 1: 1 above tau_max, 0 below tau_min, else
+ * Phi(c0 + c1 tau + c2 tau^2 (+ c3 tau^3)) with the small-p coefficients for tau <= tau*, the
+ * large-p ones above (parity note: the polynomial order is the paper's; the reference's Breeze
+ * 0.10 polyval order is unpinned). */
+int sts_adf_test(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag, int regression,
+                 double* stat, double* pvalue, int32_t* err_per_series, void* stream);
+/* t2: kpsstest(ts, method) (:359-421); regression STS_REG_C or STS_REG_CT, anything else ->
+ * STS_ERR_REQUIREMENT ("trend must be c or ct", :360).  Residuals of the OLS on 1 (C) or 1, t
+ * (CT), t = 1..T; s2 = sum of squared running sums of the residuals; lag = (int)(3 sqrt(T) / 13);
+ * long-run variance by neweyWestVarianceEstimator (:395-421); stat = s2 / lrv / T^2.  T <= the
+ * number of regressors -> STS_ERR_NOT_ENOUGH_DATA.  The reference's critical values
+ * (:328-341) are constants of the method: sparkts.stats returns them.  1e-10 relative. */
+int sts_kpss_test(const double* in, int64_t S, int64_t T, int64_t ld, int regression, double* stat,
+                  void* stream);
+/* t3: dwtest(residuals) (:241-252): sum_{i>=1} (e_i - e_{i-1})^2 / sum_i e_i^2; T >= 1. */
+int sts_dw_test(const double* in, int64_t S, int64_t T, int64_t ld, double* stat, void* stream);
+/* t4: lbtest(residuals, maxLag) (:289-298): stat = T (T + 2) sum_{k=1..maxLag} r_k^2 / (T - k)
+ * with r = autocorr(residuals, maxLag) (a8: sts_autocorr's kernels, any maxLag >= 1; maxLag < 1
+ * -> STS_ERR_BAD_ARG; maxLag >= T gives NaN, as the reference's NaN autocorrelations do);
+ * pvalue = 1 - P(maxLag / 2, stat / 2), the regularised incomplete gamma function (commons-math3
+ * ChiSquaredDistribution.cumulativeProbability), formed as one minus the CDF like the reference. */
+int sts_lb_test(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag, double* stat,
+                double* pvalue, void* stream);
+
 /* ---- synthetic panels: counter-based Philox4x32-10, bit-identical
  * to the CPU generator in oracle/, so any shard can be regenerated anywhere. ---- */
 int sts_gen_panel(double* out, int64_t s0, int64_t S, int64_t T, int64_t ld, uint64_t seed,
@@ -400,6 +451,14 @@ int sts_ar_remove_host(const double* in, double* out, int64_t S, int64_t T, int6
                        const double* c, const double* coef, int p);
 int sts_ar_add_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld,
                     const double* c, const double* coef, int p);
+/* t1-t4 (what a JNI wrapper of TimeSeriesStatisticalTests will call) */
+int sts_adf_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag, int regression,
+                      double* stat, double* pvalue, int32_t* err_per_series);
+int sts_kpss_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int regression,
+                       double* stat);
+int sts_dw_test_host(const double* in, int64_t S, int64_t T, int64_t ld, double* stat);
+int sts_lb_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag, double* stat,
+                     double* pvalue);
 
 #ifdef __cplusplus
 }

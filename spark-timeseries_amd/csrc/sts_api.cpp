@@ -1187,6 +1187,100 @@ int sts_fill_diff_ewma(const double* in, double* out, int64_t S, int64_t T, int6
     return es.finish("fill_diff_ewma");
 }
 
+// ---- statistical tests: S/stats/TimeSeriesStatisticalTests.scala (sts_stattests.hip) ----
+
+int sts_regression_from_name(const char* name) {
+    if (!name) return -2;
+    if (!std::strcmp(name, "nc")) return STS_REG_NC;
+    if (!std::strcmp(name, "c")) return STS_REG_C;
+    if (!std::strcmp(name, "ct")) return STS_REG_CT;
+    if (!std::strcmp(name, "ctt")) return STS_REG_CTT;
+    return -2;
+}
+
+static int stat_panel(const double* in, int64_t S, int64_t T, int64_t ld, const double* stat, const char* name) {
+    int r;
+    if ((r = check_panel(in, S, T, ld, name))) return r;
+    if (S > 0 && !stat) return fail(STS_ERR_BAD_ARG, "%s: null output", name);
+    if (S > 0x7fffffffLL) return fail(STS_ERR_BAD_ARG, "%s: panel too large for one launch", name);
+    return STS_OK;
+}
+
+int sts_dw_test(const double* in, int64_t S, int64_t T, int64_t ld, double* stat, void* stream) {
+    int r;
+    if ((r = stat_panel(in, S, T, ld, stat, "dwtest"))) return r;
+    if (T < 1) return fail(STS_ERR_BAD_ARG, "dwtest: empty series (residuals(0) does not exist)");
+    if (S == 0) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    sts::StatArgs a{};
+    a.in = in; a.S = S; a.T = T; a.ld = ld; a.stat = stat;
+    HIP_TRY(timed(st, [&] { return sts::launch_dw(a, st); }), "dwtest");
+    return STS_OK;
+}
+
+int sts_kpss_test(const double* in, int64_t S, int64_t T, int64_t ld, int regression, double* stat, void* stream) {
+    int r;
+    if (regression != STS_REG_C && regression != STS_REG_CT)
+        return fail(STS_ERR_REQUIREMENT, "requirement failed: trend must be c or ct");
+    if ((r = stat_panel(in, S, T, ld, stat, "kpsstest"))) return r;
+    if (T <= regression)
+        return fail(STS_ERR_NOT_ENOUGH_DATA, "kpsstest: not enough data (%lld rows) for the number of predictors (%d)",
+                    (long long)T, regression);
+    if (S == 0) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    sts::StatArgs a{};
+    a.in = in; a.S = S; a.T = T; a.ld = ld; a.stat = stat; a.q = regression;
+    a.L = (int)(3 * std::sqrt((double)T) / 13);   // :380, R tseries' default
+    HIP_TRY(timed(st, [&] { return sts::launch_kpss(a, st); }), "kpsstest");
+    return STS_OK;
+}
+
+int sts_adf_test(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag, int regression, double* stat,
+                 double* pvalue, int32_t* err_per_series, void* stream) {
+    int r;
+    if (regression < STS_REG_NC || regression > STS_REG_CTT)
+        return fail(STS_ERR_BAD_ARG, "adftest: regression %d is not nc, c, ct or ctt", regression);
+    if (max_lag < 0 || max_lag > 31) return fail(STS_ERR_BAD_ARG, "adftest: maxLag %d outside [0, 31]", max_lag);
+    if ((r = stat_panel(in, S, T, ld, stat, "adftest"))) return r;
+    const int64_t n_obs = T - 1 - max_lag, k = 1 + max_lag + regression;
+    if (n_obs <= k)
+        return fail(STS_ERR_NOT_ENOUGH_DATA, "adftest: not enough data (%lld rows) for the number of predictors (%lld)",
+                    (long long)n_obs, (long long)k);
+    if (S == 0) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    ErrSink es(err_per_series, S, st);
+    if ((r = es.prepare())) return r;
+    sts::StatArgs a{};
+    a.in = in; a.S = S; a.T = T; a.ld = ld; a.stat = stat; a.err = es.dev; a.p = max_lag; a.q = regression;
+    HIP_TRY(timed(st, [&] { return sts::launch_adf(a, st); }), "adftest");
+    if (pvalue) HIP_TRY(sts::launch_adf_pvalue(stat, pvalue, S, regression, st), "adftest (p-value)");
+    return es.finish("adftest");
+}
+
+int sts_lb_test(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag, double* stat, double* pvalue,
+                void* stream) {
+    int r;
+    if (max_lag < 1) return fail(STS_ERR_BAD_ARG, "lbtest: maxLag %d < 1", max_lag);
+    if ((r = stat_panel(in, S, T, ld, stat, "lbtest"))) return r;
+    if (T < 1) return fail(STS_ERR_BAD_ARG, "lbtest: empty series");
+    if (S == 0) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    // autocorr(residuals, maxLag) into a stream-ordered S x K scratch (a device status array keeps
+    // the ACF call from synchronising), then the epilogue
+    Scratch sc(st);
+    const size_t nacf = (size_t)S * (size_t)max_lag;
+    HIP_TRY(sc.alloc(nacf * sizeof(double) + (size_t)S * sizeof(int32_t)), "hipMallocAsync(lbtest)");
+    double* acf = static_cast<double*>(sc.p);
+    int32_t* err = reinterpret_cast<int32_t*>(acf + nacf);
+    if ((r = sts_fill_autocorr(in, nullptr, S, T, ld, ld, STS_FILL_NONE, max_lag, acf, err, st))) return r;
+    HIP_TRY(timed(st, [&] { return sts::launch_lb(acf, S, T, max_lag, stat, pvalue, st); }), "lbtest");
+    return STS_OK;
+}
+
 int sts_gen_panel(double* out, int64_t s0, int64_t S, int64_t T, int64_t ld, uint64_t seed, double nan_p,
                   void* stream) {
     int r;

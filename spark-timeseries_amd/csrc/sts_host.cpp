@@ -685,4 +685,55 @@ int sts_ar_add_host(const double* in, double* out, int64_t S, int64_t T, int64_t
     return ar_host(true, in, out, S, T, ld, c, coef, p);
 }
 
+// ---- statistical tests: every other argument error comes from staged()'s validate-only call of
+// the device entry point ----
+
+int sts_dw_test_host(const double* in, int64_t S, int64_t T, int64_t ld, double* stat) {
+    if (ld < T || T < 1 || (S > 0 && !in)) return sts_dw_test(in, S, T, ld, stat, nullptr);
+    const size_t row = (size_t)T * sizeof(double);
+    return staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(stat, sizeof(double), sizeof(double))},
+                  [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
+                      return sts_dw_test(static_cast<const double*>(d[0]), n, T, T, static_cast<double*>(d[1]), s);
+                  });
+}
+
+int sts_kpss_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int regression, double* stat) {
+    if (ld < T || T < 1 || (S > 0 && !in)) return sts_kpss_test(in, S, T, ld, regression, stat, nullptr);
+    const size_t row = (size_t)T * sizeof(double);
+    return staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(stat, sizeof(double), sizeof(double))},
+                  [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
+                      return sts_kpss_test(static_cast<const double*>(d[0]), n, T, T, regression,
+                                           static_cast<double*>(d[1]), s);
+                  });
+}
+
+int sts_adf_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag, int regression, double* stat,
+                      double* pvalue, int32_t* err) {
+    if (ld < T || T < 1 || (S > 0 && !in))
+        return sts_adf_test(in, S, T, ld, max_lag, regression, stat, pvalue, nullptr, nullptr);
+    const size_t row = (size_t)T * sizeof(double);
+    ErrOut eo(err, S);
+    const int st = staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(stat, sizeof(double), sizeof(double)),
+                              out_arg(pvalue, sizeof(double), sizeof(double)),
+                              out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
+                          [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
+                              return sts_adf_test(static_cast<const double*>(d[0]), n, T, T, max_lag, regression,
+                                                  static_cast<double*>(d[1]),
+                                                  pvalue ? static_cast<double*>(d[2]) : nullptr,
+                                                  static_cast<int32_t*>(d[3]), s);
+                          });
+    return eo.finish(st, S, "adftest");
+}
+
+int sts_lb_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag, double* stat, double* pvalue) {
+    if (ld < T || T < 1 || (S > 0 && !in)) return sts_lb_test(in, S, T, ld, max_lag, stat, pvalue, nullptr);
+    const size_t row = (size_t)T * sizeof(double);
+    return staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(stat, sizeof(double), sizeof(double)),
+                      out_arg(pvalue, sizeof(double), sizeof(double))},
+                  [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
+                      return sts_lb_test(static_cast<const double*>(d[0]), n, T, T, max_lag, static_cast<double*>(d[1]),
+                                         pvalue ? static_cast<double*>(d[2]) : nullptr, s);
+                  });
+}
+
 }  // extern "C"

@@ -205,6 +205,25 @@ struct GarchEffectsArgs {
 };
 hipError_t launch_garch_effects(int op, const GarchEffectsArgs& a, hipStream_t st);
 
+// statistical tests (sts_stattests.hip): one workgroup per series; series of up to kStatOneWave
+// steps live in one wave's LDS block, longer ones are swept from global memory
+constexpr int64_t kStatOneWave = 2560;
+struct StatArgs {
+    const double* in;
+    int64_t S, T, ld;
+    double* stat;         // S
+    int32_t* err;         // ADF: per-series status, zeroed by the caller
+    int p;                // ADF: maxLag
+    int q;                // trend columns: sts_regression's value (KPSS: 1 or 2)
+    int L;                // KPSS: Newey-West lag
+};
+hipError_t launch_dw(const StatArgs& a, hipStream_t st);
+hipError_t launch_kpss(const StatArgs& a, hipStream_t st);
+hipError_t launch_adf(const StatArgs& a, hipStream_t st);
+hipError_t launch_adf_pvalue(const double* stat, double* pv, int64_t S, int regression, hipStream_t st);
+// Ljung-Box statistic (and p-value unless pv is null) from an S x K ACF
+hipError_t launch_lb(const double* acf, int64_t S, int64_t T, int K, double* stat, double* pv, hipStream_t st);
+
 // seriesStats / removeInstantsWithNaNs / toInstants (sts_instants.hip)
 hipError_t launch_series_stats(const double* in, double* out, int64_t S, int64_t T, int64_t ld, hipStream_t st);
 hipError_t launch_nan_instants(const double* in, uint8_t* flags, int64_t S, int64_t T, int64_t ld, hipStream_t st);

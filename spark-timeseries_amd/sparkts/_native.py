@@ -92,6 +92,15 @@ SIGNATURES = {
     "sts_fill_autocorr_host": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_vp, _c_vp]),
     "sts_fill_diff_ewma_host": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_vp, _c_vp]),
     "sts_ar_fit_remove_host": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
+    "sts_regression_from_name": (_c_int, [ctypes.c_char_p]),
+    "sts_adf_test": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "sts_kpss_test": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
+    "sts_dw_test": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
+    "sts_lb_test": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_vp]),
+    "sts_adf_test_host": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
+    "sts_kpss_test_host": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
+    "sts_dw_test_host": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
+    "sts_lb_test_host": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
 }
 
 _lib = None

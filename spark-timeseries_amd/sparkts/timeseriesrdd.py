@@ -60,6 +60,27 @@ class TimeSeriesRDD:
         """rdd.mapValues(autocorr(_, numLags)) over the partition: (S, numLags)."""
         return uts.autocorr(self.data, numLags)
 
+    # --- S/stats/TimeSeriesStatisticalTests.scala over the partition panel: (S,) per result ---
+    def adftest(self, maxLag: int, regression: str = "c"):
+        """rdd.mapValues(adftest(_, maxLag, regression)): (statistics, p-values)."""
+        from .stats import TimeSeriesStatisticalTests as tst
+        return tst.adftest(self.data, maxLag, regression)
+
+    def kpsstest(self, method: str):
+        """rdd.mapValues(kpsstest(_, method)): (statistics, critical values)."""
+        from .stats import TimeSeriesStatisticalTests as tst
+        return tst.kpsstest(self.data, method)
+
+    def dwtest(self):
+        """rdd.mapValues(dwtest(_)): Durbin-Watson statistics."""
+        from .stats import TimeSeriesStatisticalTests as tst
+        return tst.dwtest(self.data)
+
+    def lbtest(self, maxLag: int):
+        """rdd.mapValues(lbtest(_, maxLag)): (statistics, p-values)."""
+        from .stats import TimeSeriesStatisticalTests as tst
+        return tst.lbtest(self.data, maxLag)
+
     def fillAndAutocorr(self, method: str, numLags: int):
         """fill(method) followed by autocorr of every filled series, fused into one pass
         over HBM.  Returns (filled TimeSeriesRDD, acf (S, K))."""

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Time the batched statistical tests (sts_dw_test, sts_kpss_test, sts_adf_test, sts_lb_test) at
+the flagship panel shapes, next to three yardsticks measured in the SAME process, alternating
+call by call with the case being measured:
+
+  sts_series_stats   the one-read kernel on the same panel (the rate a one-sweep kernel can reach)
+  sts_autocorr       at the Ljung-Box K (what sts_lb_test adds is the epilogue)
+  torch              Durbin-Watson composed from torch ops on the device
+
+HIP events around every call, every shape warmed up first, --reps timed calls per case (>= 20).
+One JSON line per case: median / min ms, the yardstick's, their ratio, achieved bytes/s
+(8 S T over the median) and the library's sha256.
+
+    python tools/stattests_timing.py [--reps 20] [--out profiles/stattests_timing.jsonl]
+"""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "spark-timeseries_amd"))
+
+SHAPES = [(1_000_000, 390), (500_000, 2520)]
+REG_C, REG_CT = 1, 2
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--scale", type=float, default=1.0, help="scale S (a quick look on a busy machine)")
+    a = ap.parse_args()
+    assert a.reps >= 20 or a.scale != 1.0, "at least 20 timed calls per case"
+    import torch
+    from sparkts import _native
+    _native.ensure_device(0)
+    lib = _native.lib()
+    with open(_native.LIB_PATH, "rb") as f:
+        lib_hash = hashlib.sha256(f.read()).hexdigest()[:16]
+    sp = torch.cuda.current_stream().cuda_stream
+    out = open(a.out, "w") if a.out else None
+
+    def timed_pair(fn, yard, reps):
+        """Alternate fn / yard, one event pair per call -> (list of ms, list of ms)."""
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(reps)]
+        for _ in range(3):
+            assert fn() == 0
+            yard()
+        torch.cuda.synchronize()
+        for e in ev:
+            e[0].record()
+            assert fn() == 0
+            e[1].record()
+            e[2].record()
+            yard()
+            e[3].record()
+        torch.cuda.synchronize()
+        return [e[0].elapsed_time(e[1]) for e in ev], [e[2].elapsed_time(e[3]) for e in ev]
+
+    def med(v):
+        return sorted(v)[len(v) // 2]
+
+    for S, T in SHAPES:
+        S = max(1, int(S * a.scale))
+        x = torch.empty((S, T), dtype=torch.float64, device="cuda")
+        assert lib.sts_gen_panel(x.data_ptr(), 0, S, T, T, 6, 0.0, sp) == 0
+        stat = torch.empty(S, dtype=torch.float64, device="cuda")
+        pv = torch.empty(S, dtype=torch.float64, device="cuda")
+        st4 = torch.empty((S, 4), dtype=torch.float64, device="cuda")
+        K = 20
+        acf = torch.empty((S, K), dtype=torch.float64, device="cuda")
+        err = torch.zeros(S, dtype=torch.int32, device="cuda")
+        X = x.data_ptr()
+
+        def series_stats():
+            assert lib.sts_series_stats(X, S, T, T, st4.data_ptr(), sp) == 0
+
+        def autocorr():
+            assert lib.sts_fill_autocorr(X, None, S, T, T, T, -1, K, acf.data_ptr(), err.data_ptr(), sp) == 0
+
+        def torch_dw():
+            d = x[:, 1:] - x[:, :-1]
+            return (d * d).sum(dim=1) / (x * x).sum(dim=1)
+
+        cases = [
+            ("dw", lambda: lib.sts_dw_test(X, S, T, T, stat.data_ptr(), sp), series_stats, "sts_series_stats"),
+            ("dw_vs_torch", lambda: lib.sts_dw_test(X, S, T, T, stat.data_ptr(), sp), torch_dw, "torch"),
+            ("kpss_c", lambda: lib.sts_kpss_test(X, S, T, T, REG_C, stat.data_ptr(), sp), series_stats, "sts_series_stats"),
+            ("kpss_ct", lambda: lib.sts_kpss_test(X, S, T, T, REG_CT, stat.data_ptr(), sp), series_stats, "sts_series_stats"),
+            ("adf_1_c", lambda: lib.sts_adf_test(X, S, T, T, 1, REG_C, stat.data_ptr(), pv.data_ptr(), err.data_ptr(), sp),
+             series_stats, "sts_series_stats"),
+            ("adf_5_ct", lambda: lib.sts_adf_test(X, S, T, T, 5, REG_CT, stat.data_ptr(), pv.data_ptr(), err.data_ptr(), sp),
+             series_stats, "sts_series_stats"),
+            ("lb_20", lambda: lib.sts_lb_test(X, S, T, T, K, stat.data_ptr(), pv.data_ptr(), sp), autocorr, "sts_autocorr"),
+            ("lb_20_vs_stats", lambda: lib.sts_lb_test(X, S, T, T, K, stat.data_ptr(), pv.data_ptr(), sp), series_stats,
+             "sts_series_stats"),
+        ]
+        for name, fn, yard, yname in cases:
+            ms, yms = timed_pair(fn, yard, a.reps)
+            rec = {"case": name, "S": S, "T": T, "reps": a.reps, "ms_median": med(ms), "ms_min": min(ms),
+                   "yardstick": yname, "yard_ms_median": med(yms), "yard_ms_min": min(yms),
+                   "ratio_to_yardstick": med(ms) / med(yms), "GBps": 8.0 * S * T / (med(ms) * 1e-3) / 1e9,
+                   "lib_sha256": lib_hash}
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if out:
+                out.write(line + "\n")
+                out.flush()
+        del x, stat, pv, st4, acf, err
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
