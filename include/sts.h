@@ -300,6 +300,63 @@ int sts_arima_fit_ar(const double* in, int64_t S, int64_t T, int64_t ld, int p, 
                      int include_intercept, double* c, double* coef, int32_t* err_per_series,
                      void* stream);
 
+/* ---- f1c: ARIMA(p, d, q) with MA terms -- the "css-cgd" fit, the CSS likelihood, the
+ * time-dependent effects and forecasts (S/models/ARIMA.scala), batched over a panel.
+ * Orders: 0 <= p, q <= STS_ARIMA_MAX_ORDER, n = include_intercept + p + q >= 1, 0 <= d <= T;
+ * anything else -> STS_ERR_BAD_ARG.  Coefficients are per series, (S, n) row-major, in
+ * ARIMAModel.coefficients' order: intercept (if any), AR by increasing lag, MA by increasing
+ * lag.  Differencing is differencesOfOrderD (S/UnivariateTimeSeries.scala:438-450) and the
+ * models work on its .drop(d) view, as fitModel (:82) and logLikelihoodCSS (:267) do.
+ * `_host` variants and JNI bindings do not exist for these entry points. */
+#define STS_ARIMA_MAX_ORDER 4
+/* HannanRissanenInit (:207-233): AR(m) with intercept on the differenced series, m = max(p, q)
+ * + 1 (Autoregression.fitModel, as sts_ar_fit), its one-step errors, then the OLS of
+ * yTrunc.drop(m - 1) on [1 if intercept, p lags of yTrunc, q lags of the errors] with the rows
+ * trimmed as :225-227.  init_out is (S, n).  Either regression with fewer rows than predictors
+ * -> STS_ERR_NOT_ENOUGH_DATA for the call; per series STS_ERR_SINGULAR (and NaN coefficients).
+ * The second regression is solved on centred columns through a Cholesky factor: 1e-10
+ * relative to commons-math3's Householder QR, measured against the series' largest
+ * coefficient, on designs whose column-scaled condition number is at most 1e4. */
+int sts_arima_hr_init(const double* in, int64_t S, int64_t T, int64_t ld, int p, int d, int q,
+                      int include_intercept, double* init_out, int32_t* err_per_series,
+                      void* stream);
+/* fitWithCSSCGD (:166-192) from init (S, n): commons-math3's NonLinearConjugateGradientOptimizer
+ * (Fletcher-Reeves, SimpleValueChecker(1e-7, 1e-7), MaxIter / MaxEval 10000, MAXIMIZE) run per
+ * series on the device, every objective / gradient evaluation in the reference's operation
+ * order, so the optimizer takes the reference's path: coef_out (S, n) is bit-exact given
+ * init.  err_per_series as sts_garch_fit (STS_ERR_TOO_MANY_EVALUATIONS, ...; that series'
+ * coefficients are NaN); evals (S int32, may be NULL) receives the objective evaluations
+ * commons-math3 counts. */
+int sts_arima_fit_css(const double* in, int64_t S, int64_t T, int64_t ld, int p, int d, int q,
+                      int include_intercept, const double* init, double* coef_out,
+                      int32_t* err_per_series, int32_t* evals, void* stream);
+/* ARIMAModel.logLikelihoodCSS (:266-269 over logLikelihoodCSSARMA :278-293) and
+ * gradientlogLikelihoodCSSARMA (:312-381) of the series differenced by d, at coef (S, n).
+ * loglik (S) or grad (S, n) may be NULL.  Bit-exact (Math.log as StrictMath.log).  Parity
+ * note: the shift of dEdTheta (:373) is taken as the row shift its comment describes; the
+ * reference's Breeze overlapping-slice assignment could not be run here. */
+int sts_arima_css_loglik_gradient(const double* in, int64_t S, int64_t T, int64_t ld, int p, int d,
+                                  int q, int include_intercept, const double* coef, double* loglik,
+                                  double* grad, void* stream);
+/* ARIMAModel.removeTimeDependentEffects (:474-487) and addTimeDependentEffects (:498-510;
+ * inverseDifferencesOfOrderD, S/UnivariateTimeSeries.scala:459-470).  The reference computes
+ * on copies, so out == in (with ld_in == ld_out) gives the out-of-place result.  Bit-exact. */
+int sts_arima_remove(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in,
+                     int64_t ld_out, int p, int d, int q, int include_intercept, const double* coef,
+                     void* stream);
+int sts_arima_add(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in,
+                  int64_t ld_out, int p, int d, int q, int include_intercept, const double* coef,
+                  void* stream);
+/* ARIMAModel.forecast(ts, nFuture) (:537-605): out is (S, T + n_future), ld_out >= T + n_future;
+ * the first d values copied, the fitted one-step values re-integrated through the difference
+ * orders (:571-592), then n_future steps with zero future errors (:556-561, :593-602).  out
+ * must not alias in.  Bit-exact for d <= 2.  Parity note: sum(diffMatrix(0 until d, i - 1)) (:591) is added in increasing
+ * difference order; for d >= 3 Breeze's order of that sum could not be confirmed (the two
+ * can differ by an ulp or two there). */
+int sts_arima_forecast(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in,
+                       int64_t ld_out, int p, int d, int q, int include_intercept,
+                       const double* coef, int n_future, void* stream);
+
 /* ---- a12 / a13: ARModel.remove/addTimeDependentEffects (S/models/Autoregression.scala:60-88).
  * out == in reproduces the reference's aliasing semantics.  Bit-exact. */
 int sts_ar_remove(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in,

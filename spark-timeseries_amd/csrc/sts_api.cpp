@@ -1137,6 +1137,227 @@ int sts_arima_fit_ar(const double* in, int64_t S, int64_t T, int64_t ld, int p, 
     return sts_ar_fit(cur + d, S, Tn, T, p, include_intercept ? 0 : 1, c, coef, err_per_series, stream);
 }
 
+// ---- ARIMA(p, d, q) with MA terms: S/models/ARIMA.scala (sts_arima.hip) ----
+
+namespace {
+
+int arima_orders(const char* name, int64_t T, int p, int d, int q, int* n) {
+    if (p < 0 || p > STS_ARIMA_MAX_ORDER || q < 0 || q > STS_ARIMA_MAX_ORDER)
+        return fail(STS_ERR_BAD_ARG, "%s: orders p=%d, q=%d outside [0, %d]", name, p, q, STS_ARIMA_MAX_ORDER);
+    if (d < 0 || d > T) return fail(STS_ERR_BAD_ARG, "%s: differencing order %d outside [0, T]", name, d);
+    if (*n < 1) return fail(STS_ERR_BAD_ARG, "%s: a model without intercept, AR and MA terms has no coefficients", name);
+    return STS_OK;
+}
+
+// differencesOfOrderD (S/UnivariateTimeSeries.scala:438-450): level i differences level i-1 at
+// lag 1 from index i (ping-pong into packed scratch, as sts_arima_fit_ar)
+struct ArimaDiff {
+    Scratch a, b;
+    const double* cur = nullptr;
+    int64_t ld = 0;
+    explicit ArimaDiff(hipStream_t st) : a(st), b(st) {}
+    int run(const double* in, int64_t S, int64_t T, int64_t ld_in, int d, hipStream_t st) {
+        cur = in;
+        ld = ld_in;
+        if (d == 0 || S * T == 0) return STS_OK;
+        HIP_TRY(a.alloc((size_t)(S * T) * sizeof(double)), "hipMallocAsync(arima)");
+        if (d > 1) HIP_TRY(b.alloc((size_t)(S * T) * sizeof(double)), "hipMallocAsync(arima)");
+        double* bufs[2] = {static_cast<double*>(a.p), static_cast<double*>(b.p)};
+        for (int i = 1; i <= d; i++) {
+            double* nxt = bufs[(i - 1) & 1];
+            HIP_TRY(sts::launch_diff(cur, nxt, S, T, ld, T, 1, i, st), "differencesOfOrderD");
+            cur = nxt;
+            ld = T;
+        }
+        return STS_OK;
+    }
+};
+
+}  // namespace
+
+int sts_arima_hr_init(const double* in, int64_t S, int64_t T, int64_t ld, int p, int d, int q, int include_intercept,
+                      double* init_out, int32_t* err_per_series, void* stream) {
+    const char* name = "ARIMA.HannanRissanenInit";
+    int r, n = (include_intercept ? 1 : 0) + p + q;
+    if ((r = check_panel(in, S, T, ld, name))) return r;
+    if ((r = arima_orders(name, T, p, d, q, &n))) return r;
+    if (S > 0 && !init_out) return fail(STS_ERR_BAD_ARG, "%s: null output", name);
+    const int maxLag = p > q ? p : q, m = maxLag + 1;
+    const int64_t N = T - d;
+    if (N - m < (int64_t)m + 1)
+        return fail(STS_ERR_NOT_ENOUGH_DATA, "%s: not enough data (%lld rows) for the number of predictors (%d)", name,
+                    (long long)(N - m), m);
+    if (N - m - maxLag < (int64_t)p + q + 1)
+        return fail(STS_ERR_NOT_ENOUGH_DATA, "%s: not enough data (%lld rows) for the number of predictors (%d)", name,
+                    (long long)(N - m - maxLag), p + q);
+    if (S == 0) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    ErrSink es(err_per_series, S, st);
+    if ((r = es.prepare())) return r;
+    ArimaDiff df(st);
+    if ((r = df.run(in, S, T, ld, d, st))) return r;
+    // stage one: Autoregression.fitModel(y, m) on the .drop(d) view
+    Scratch arbuf(st);
+    HIP_TRY(arbuf.alloc((size_t)S * (size_t)(m + 1) * sizeof(double)), "hipMallocAsync(arima)");
+    double* c = static_cast<double*>(arbuf.p);
+    double* phi = c + S;
+    sts::ArArgs ar{};
+    ar.in = df.cur + d; ar.c = c; ar.coef = phi; ar.err = es.dev;
+    ar.S = S; ar.T = N; ar.ld_in = df.ld; ar.ld_out = N; ar.p = m; ar.no_intercept = 0;
+    HIP_TRY(timed(st, [&] { return sts::launch_ar_fit(ar, st); }), "ARIMA.HannanRissanenInit (AR stage)");
+    sts::ArimaHrArgs h{};
+    h.in = df.cur + d; h.S = S; h.ld = df.ld; h.n_len = (int)N; h.p = p; h.q = q; h.icpt = include_intercept ? 1 : 0;
+    h.c = c; h.phi = phi; h.init_out = init_out; h.err = es.dev;
+    HIP_TRY(timed(st, [&] { return sts::launch_arima_hr(h, st); }), name);
+    return es.finish(name);
+}
+
+int sts_arima_fit_css(const double* in, int64_t S, int64_t T, int64_t ld, int p, int d, int q, int include_intercept,
+                      const double* init, double* coef_out, int32_t* err_per_series, int32_t* evals, void* stream) {
+    const char* name = "ARIMA.fitModel(css-cgd)";
+    int r, n = (include_intercept ? 1 : 0) + p + q;
+    if ((r = check_panel(in, S, T, ld, name))) return r;
+    if ((r = arima_orders(name, T, p, d, q, &n))) return r;
+    if (S > 0 && (!init || !coef_out)) return fail(STS_ERR_BAD_ARG, "%s: null start or output", name);
+    if (S == 0) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    ErrSink es(err_per_series, S, st);
+    if ((r = es.prepare())) return r;
+    ArimaDiff df(st);
+    if ((r = df.run(in, S, T, ld, d, st))) return r;
+    sts::ArimaCssArgs a{};
+    a.in = df.cur + d; a.S = S; a.ld = df.ld; a.n_len = (int)(T - d); a.p = p; a.q = q;
+    a.icpt = include_intercept ? 1 : 0; a.coef_in = init; a.coef_out = coef_out; a.err = es.dev; a.evals = evals;
+    HIP_TRY(timed(st, [&] { return sts::launch_arima_css(a, true, st); }), name);
+    return es.finish(name);
+}
+
+int sts_arima_css_loglik_gradient(const double* in, int64_t S, int64_t T, int64_t ld, int p, int d, int q,
+                                  int include_intercept, const double* coef, double* loglik, double* grad,
+                                  void* stream) {
+    const char* name = "ARIMAModel.logLikelihoodCSS";
+    int r, n = (include_intercept ? 1 : 0) + p + q;
+    if ((r = check_panel(in, S, T, ld, name))) return r;
+    if ((r = arima_orders(name, T, p, d, q, &n))) return r;
+    if (S > 0 && !coef) return fail(STS_ERR_BAD_ARG, "%s: null coefficients", name);
+    if (S == 0 || (!loglik && !grad)) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    ArimaDiff df(st);
+    if ((r = df.run(in, S, T, ld, d, st))) return r;
+    sts::ArimaCssArgs a{};
+    a.in = df.cur + d; a.S = S; a.ld = df.ld; a.n_len = (int)(T - d); a.p = p; a.q = q;
+    a.icpt = include_intercept ? 1 : 0; a.coef_in = coef; a.loglik = loglik; a.grad = grad;
+    HIP_TRY(timed(st, [&] { return sts::launch_arima_css(a, false, st); }), name);
+    return STS_OK;
+}
+
+static int arima_effects(bool add, const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out,
+                         int p, int d, int q, int include_intercept, const double* coef, void* stream) {
+    const char* name = add ? "ARIMAModel.addTimeDependentEffects" : "ARIMAModel.removeTimeDependentEffects";
+    int r, n = (include_intercept ? 1 : 0) + p + q;
+    if ((r = check_panel(in, S, T, ld_in, name))) return r;
+    if (!out) return fail(STS_ERR_NULL_DEST, "%s: dest is null (the reference writes into dest)", name);
+    if ((r = check_panel(out, S, T, ld_out, name))) return r;
+    if ((r = arima_orders(name, T, p, d, q, &n))) return r;
+    if (S > 0 && !coef) return fail(STS_ERR_BAD_ARG, "%s: null coefficients", name);
+    if (S * T == 0) return STS_OK;
+    if (in == out && ld_in != ld_out) return fail(STS_ERR_BAD_ARG, "%s: in place needs ld_in == ld_out", name);
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    sts::ArimaEffectsArgs a{};
+    a.out = out; a.S = S; a.T = T; a.ld_out = ld_out; a.p = p; a.q = q; a.icpt = include_intercept ? 1 : 0;
+    a.coef = coef;
+    if (!add) {
+        ArimaDiff df(st);   // differencesOfOrderD(ts, d), all T values (:476)
+        if ((r = df.run(in, S, T, ld_in, d, st))) return r;
+        a.in = df.cur; a.ld_in = df.ld;
+        HIP_TRY(timed(st, [&] { return sts::launch_arima_effects(sts::kArimaRemove, a, st); }), name);
+        return STS_OK;
+    }
+    a.in = in; a.ld_in = ld_in;
+    HIP_TRY(timed(st, [&] { return sts::launch_arima_effects(sts::kArimaAdd, a, st); }), name);
+    // inverseDifferencesOfOrderD (:508): inverseDifferencesAtLag(x, x, 1, i) for i = d .. 1
+    a.in = out; a.ld_in = ld_out;
+    for (int i = d; i >= 1; i--) {
+        a.start = i;
+        HIP_TRY(sts::launch_arima_effects(sts::kArimaIntegrate, a, st), name);
+    }
+    return STS_OK;
+}
+
+int sts_arima_remove(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int p, int d,
+                     int q, int include_intercept, const double* coef, void* stream) {
+    return arima_effects(false, in, out, S, T, ld_in, ld_out, p, d, q, include_intercept, coef, stream);
+}
+
+int sts_arima_add(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int p, int d,
+                  int q, int include_intercept, const double* coef, void* stream) {
+    return arima_effects(true, in, out, S, T, ld_in, ld_out, p, d, q, include_intercept, coef, stream);
+}
+
+int sts_arima_forecast(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int p, int d,
+                       int q, int include_intercept, const double* coef, int n_future, void* stream) {
+    const char* name = "ARIMAModel.forecast";
+    int r, n = (include_intercept ? 1 : 0) + p + q;
+    if (n_future < 0) return fail(STS_ERR_BAD_ARG, "%s: negative nFuture", name);
+    const int64_t TO = T + n_future;
+    if ((r = check_panel(in, S, T, ld_in, name))) return r;
+    if (!out) return fail(STS_ERR_BAD_ARG, "%s: null output", name);
+    if ((r = check_panel(out, S, TO, ld_out, name))) return r;
+    if ((r = arima_orders(name, T, p, d, q, &n))) return r;
+    if (S > 0 && !coef) return fail(STS_ERR_BAD_ARG, "%s: null coefficients", name);
+    if (S * TO > 0 && static_cast<const void*>(in) == out) return fail(STS_ERR_BAD_ARG, "%s: out must not alias in", name);
+    if (S * TO == 0) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    ArimaDiff df(st);
+    if ((r = df.run(in, S, T, ld_in, d, st))) return r;
+    sts::ArimaForecastArgs a{};
+    a.ts = in; a.diffed = df.cur; a.S = S; a.T = T; a.ld_ts = ld_in; a.ld_d = df.ld; a.d = d; a.n_future = n_future;
+    a.p = p; a.q = q; a.icpt = include_intercept ? 1 : 0; a.coef = coef;
+    if (d == 0) {
+        a.out = out; a.ld_out = ld_out;
+        HIP_TRY(timed(st, [&] { return sts::launch_arima_forecast(a, st); }), name);
+        return STS_OK;
+    }
+    // d > 0 (:571-603): the raw forecast, then the sums of the difference levels 0 .. d-1, the
+    // diagonal of their last d columns, the merge and the inverse differencing of the tail
+    Scratch raw(st), sum(st), diag(st), lv0(st), lv1(st);
+    HIP_TRY(raw.alloc((size_t)(S * TO) * sizeof(double)), "hipMallocAsync(arima)");
+    HIP_TRY(sum.alloc((size_t)(S * T) * sizeof(double)), "hipMallocAsync(arima)");
+    HIP_TRY(diag.alloc((size_t)(S * d) * sizeof(double)), "hipMallocAsync(arima)");
+    if (d > 1) HIP_TRY(lv0.alloc((size_t)(S * T) * sizeof(double)), "hipMallocAsync(arima)");
+    if (d > 2) HIP_TRY(lv1.alloc((size_t)(S * T) * sizeof(double)), "hipMallocAsync(arima)");
+    a.out = static_cast<double*>(raw.p); a.ld_out = TO;
+    HIP_TRY(timed(st, [&] { return sts::launch_arima_forecast(a, st); }), name);
+    const double* level = in;
+    int64_t lld = ld_in;
+    double* lbufs[2] = {static_cast<double*>(lv0.p), static_cast<double*>(lv1.p)};
+    for (int k = 0; k < d; k++) {
+        if (k > 0) {   // diffMatrix(k, k to -1) = differencesOfOrderD(diffMatrix(k - 1, k to -1), 1) (:582)
+            double* nxt = lbufs[(k - 1) & 1];
+            HIP_TRY(sts::launch_diff(level, nxt, S, T, lld, T, 1, k + 1, st), name);
+            level = nxt;
+            lld = T;
+        }
+        HIP_TRY(sts::launch_arima_level_sum(level, lld, static_cast<double*>(sum.p), S, T, k == 0, st), name);
+        HIP_TRY(sts::launch_arima_diag(level, lld, S, T - d + k, static_cast<double*>(diag.p), d, k, st), name);
+    }
+    HIP_TRY(sts::launch_arima_forecast_merge(in, ld_in, static_cast<const double*>(sum.p),
+                                             static_cast<const double*>(raw.p), static_cast<const double*>(diag.p),
+                                             out, ld_out, S, T, d, n_future, st), name);
+    sts::ArimaEffectsArgs e{};
+    e.in = out + (T - d); e.out = out + (T - d); e.S = S; e.T = d + n_future; e.ld_in = ld_out; e.ld_out = ld_out;
+    for (int i = d; i >= 1; i--) {
+        e.start = i;
+        HIP_TRY(sts::launch_arima_effects(sts::kArimaIntegrate, e, st), name);
+    }
+    return STS_OK;
+}
+
 int sts_fill_diff_ewma(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int method,
                        int lag, const double* smoothing, int32_t* err_per_series, void* stream) {
     int r;

@@ -205,6 +205,64 @@ struct GarchEffectsArgs {
 };
 hipError_t launch_garch_effects(int op, const GarchEffectsArgs& a, hipStream_t st);
 
+// ARIMA(p, d, q) with MA terms (sts_arima.hip).  Every launcher works on ARMA level: the
+// C-ABI layer differences the panel (launch_diff ping-pong) and passes the view it needs.
+struct ArimaCssArgs {
+    const double* in;     // the differenced series, .drop(d) applied: S x n_len, ld
+    int64_t S, ld;
+    int n_len;
+    int p, q, icpt;
+    const double* coef_in;   // S x n: the start (fit) or the evaluation point
+    double* coef_out;        // fit: S x n
+    int32_t* err;            // fit: per-series status (optional)
+    int32_t* evals;          // fit: commons-math3 evaluation count (optional)
+    double* loglik;          // evaluation: S (optional)
+    double* grad;            // evaluation: S x n (optional)
+};
+hipError_t launch_arima_css(const ArimaCssArgs& a, bool fit, hipStream_t st);
+// steps of a series one LDS chunk of arima_css_kernel holds (the tests straddle it)
+constexpr int kArimaChunk = 64;
+enum ArimaOp { kArimaRemove = 0, kArimaAdd = 1, kArimaIntegrate = 2 };
+struct ArimaEffectsArgs {
+    const double* in;     // remove: differencesOfOrderD(ts, d), full length
+    double* out;          // may be in
+    int64_t S, T, ld_in, ld_out;
+    int p, q, icpt;
+    const double* coef;   // S x n
+    int start;            // kArimaIntegrate: inverseDifferencesAtLag(x, x, 1, start)
+};
+hipError_t launch_arima_effects(int op, const ArimaEffectsArgs& a, hipStream_t st);
+struct ArimaForecastArgs {
+    const double* ts;       // the panel: S x T, ld_ts
+    const double* diffed;   // differencesOfOrderD(ts, d), full length (ts itself for d = 0)
+    double* out;            // S x (T + n_future): the fitted differences and the forward curve
+    int64_t S, T, ld_ts, ld_d, ld_out;
+    int d, n_future;
+    int p, q, icpt;
+    const double* coef;
+};
+hipError_t launch_arima_forecast(const ArimaForecastArgs& a, hipStream_t st);
+// forecast with d > 0 (S/models/ARIMA.scala:571-603): sum += level (first: sum = 0.0 + level);
+// diag[s * d + k] = level(s, col); and the merge of ts, sum, the raw forecast and diag into out
+hipError_t launch_arima_level_sum(const double* level, int64_t ld, double* sum, int64_t S, int64_t T, int first,
+                                  hipStream_t st);
+hipError_t launch_arima_diag(const double* level, int64_t ld, int64_t S, int64_t col, double* diag, int d, int k,
+                             hipStream_t st);
+hipError_t launch_arima_forecast_merge(const double* ts, int64_t ld_ts, const double* sum, const double* raw,
+                                       const double* diag, double* out, int64_t ld_out, int64_t S, int64_t T, int d,
+                                       int n_future, hipStream_t st);
+struct ArimaHrArgs {
+    const double* in;     // the differenced series, .drop(d) applied
+    int64_t S, ld;
+    int n_len;
+    int p, q, icpt;
+    const double* c;      // the AR(m) stage, m = max(p, q) + 1: intercepts S, coefficients S x m
+    const double* phi;
+    double* init_out;     // S x n
+    int32_t* err;         // optional; a nonzero entry (the AR stage's) is kept
+};
+hipError_t launch_arima_hr(const ArimaHrArgs& a, hipStream_t st);
+
 // statistical tests (sts_stattests.hip): one workgroup per series; series of up to kStatOneWave
 // steps live in one wave's LDS block, longer ones are swept from global memory
 constexpr int64_t kStatOneWave = 2560;

@@ -69,6 +69,17 @@ SIGNATURES = {
     "sts_observations_to_panel": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
     "sts_csv_parse": (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64]),
     "sts_arima_fit_ar": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "sts_arima_hr_init": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
+    "sts_arima_fit_css": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp,
+                                   _c_vp, _c_vp]),
+    "sts_arima_css_loglik_gradient": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_vp,
+                                               _c_vp, _c_vp, _c_vp]),
+    "sts_arima_remove": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_vp,
+                                  _c_vp]),
+    "sts_arima_add": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_vp,
+                               _c_vp]),
+    "sts_arima_forecast": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_vp,
+                                    _c_int, _c_vp]),
     "sts_gen_panel": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.c_uint64, _c_dbl, _c_vp]),
     "sts_gen_ar_panel": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.c_uint64, _c_int, _c_vp]),
     "sts_fill_host": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
