@@ -69,6 +69,7 @@ __device__ __forceinline__ void lds_barrier() {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2v __attribute__((ext_vector_type(2)));   // 16-B lag-matrix stores
+typedef int i4v __attribute__((ext_vector_type(4)));      // 16-B reads of the word-offset tables
 
 constexpr int kThreads = 256;
 constexpr int kBig = 1 << 30;
@@ -210,7 +211,15 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
     __shared__ unsigned long long mask[NW];
     __shared__ int lastUpTo[NW];           // last valid E-position in words <= w (-1: none)
     __shared__ int firstFrom[NW];          // first valid E-position in words >= w (kBig: none)
-    __shared__ int wbase[NW + 1];          // NaN-list offset of each word (exclusive prefix count)
+    // NaN-list offset of each word (exclusive prefix count; [NW] = the NaN count), in groups of
+    // 8 entries = two 16-B reads, with the offset of every group's first word again in wcoarse
+    // (one 16-B read per 4 groups): the imputation phase finds the word of list entry idx in two
+    // dependent LDS round trips.  The entries past [NW] and past the last group are never
+    // rewritten: kBig, set once (> any idx).
+    constexpr int NG = NW / 8 + 1;         // groups holding entries 0 .. NW
+    constexpr int NGQ = (NG + 3) / 4;      // 16-B reads covering wcoarse
+    __shared__ __attribute__((aligned(16))) int wbase[8 * NG];
+    __shared__ __attribute__((aligned(16))) int wcoarse[4 * NGQ];
     __shared__ unsigned long long wneed[NW];   // NaN positions to impute, per word
     __shared__ int sh_i[4];                // lext, next (series positions), NaN count, long-run flag
     __shared__ double sh_d[3];             // (unused), value at lext, value at next
@@ -251,6 +260,10 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
     if (tid == 0) {
         sh_c[0] = -kBig;
         sh_c[2] = -1;
+    }
+    if (tid < 8) {   // the sentinels of the word lookup (at most 7 + 3 entries)
+        if (NW + 1 + tid < 8 * NG) wbase[NW + 1 + tid] = kBig;
+        if (NG + tid < 4 * NGQ) wcoarse[NG + tid] = kBig;
     }
     double acc_s = 0.0, acc_q = 0.0;   // sum y, sum y^2 over this thread's middle positions
 
@@ -549,6 +562,7 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
                 firstFrom[w0] = f0 < a0 ? f0 : a0;
                 wbase[w0] = exc;
                 wneed[w0] = n0;
+                if ((lane & 3) == 0) wcoarse[lane >> 2] = exc;   // word 8g is lane 4g's first word
             }
             if (w1 < NW) {
                 const int a1 = ex > l0 ? ex : l0;
@@ -582,6 +596,7 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
             }
             if (lane == 0) {
                 wbase[NW] = nnan;
+                if constexpr (NW % 8 == 0) wcoarse[NW / 8] = nnan;
                 sh_i[0] = lext;
                 sh_i[1] = next;
                 sh_i[2] = nnan;
@@ -615,36 +630,50 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
             auto impute = [&](auto long_tag) {
             constexpr bool LONG = decltype(long_tag)::value;
             for (int idx = tid; idx < nnan; idx += kThreads) {
-                // the word holding NaN #idx: last w with wbase[w] <= idx (binary search) ...
-                int lo = 0, hi = NW;
-                while (hi - lo > 1) {
-                    const int mid = (lo + hi) >> 1;
-                    if (wbase[mid] <= idx) lo = mid;
-                    else hi = mid;
+                // the word holding NaN #idx: last w with wbase[w] <= idx.  The offsets never
+                // decrease, so that is a count of entries <= idx: first over the groups' first
+                // words (wcoarse: NGQ independent 16-B reads of lane-uniform addresses; its
+                // entry 0 is 0 <= idx), then over the 8 entries of that group (two 16-B reads;
+                // its entry 0 is the group's wcoarse entry <= idx).  wbase[NW] = nnan > idx and
+                // the sentinels behind it keep the count below NW.
+                const i4v* c4 = reinterpret_cast<const i4v*>(wcoarse);
+                int g = -1;
+#pragma unroll
+                for (int j = 0; j < NGQ; j++) {
+                    const i4v c = c4[j];
+                    g += (c.x <= idx) + (c.y <= idx) + (c.z <= idx) + (c.w <= idx);
                 }
+                const i4v* b4 = reinterpret_cast<const i4v*>(wbase) + 2 * g;
+                const i4v ba = b4[0], bb = b4[1];
+                const int w = 8 * g - 1 + (ba.x <= idx) + (ba.y <= idx) + (ba.z <= idx) + (ba.w <= idx) +
+                              (bb.x <= idx) + (bb.y <= idx) + (bb.z <= idx) + (bb.w <= idx);
+                // everything the entry needs of its word, read together (clamped neighbours: the
+                // values are used only where the neighbour exists)
+                unsigned long long nm = wneed[w];
+                const int wb = wbase[w];
+                const unsigned long long m = mask[w];
+                const int lup = needL ? lastUpTo[w > 0 ? w - 1 : 0] : -1;
+                const int ffr = needN ? firstFrom[w + 1 < NW ? w + 1 : NW - 1] : kBig;
                 // ... and the position of its (idx - wbase[w])-th set need-bit (popcount bisection)
-                unsigned long long nm = wneed[lo];
-                int kk = idx - wbase[lo], bit = 0;
+                int kk = idx - wb, b = 0;
 #pragma unroll
                 for (int width = 32; width >= 1; width >>= 1) {
                     const int c = __popcll(nm & ((1ull << width) - 1ull));
-                    if (kk >= c) { kk -= c; nm >>= width; bit += width; }
+                    if (kk >= c) { kk -= c; nm >>= width; b += width; }
                 }
-                const int q = lo * 64 + bit;
+                const int q = w * 64 + b;
                 const int t = e0 + q;
-                const int w = q >> 6, b = q & 63;
-                const unsigned long long m = mask[w];
                 int Lt = -1, Nt = (int)T;
                 double Lv = 0.0, Nv = 0.0;
                 if (needL) {
                     const unsigned long long lo = m & ((1ull << b) - 1ull);
-                    const int Lq = lo ? w * 64 + 63 - __clzll(lo) : (w > 0 ? lastUpTo[w - 1] : -1);
+                    const int Lq = lo ? w * 64 + 63 - __clzll(lo) : (w > 0 ? lup : -1);
                     if (Lq >= 0) { Lt = e0 + Lq; Lv = vals[px(Lq)]; }
                     else { Lt = lext; Lv = lextv; }
                 }
                 if (needN) {
                     const unsigned long long hi = (b == 63) ? 0ull : (m & (~0ull << (b + 1)));
-                    const int Nq = hi ? w * 64 + __ffsll(hi) - 1 : (w + 1 < NW ? firstFrom[w + 1] : kBig);
+                    const int Nq = hi ? w * 64 + __ffsll(hi) - 1 : (w + 1 < NW ? ffr : kBig);
                     if (Nq < kBig) { Nt = e0 + Nq; Nv = vals[px(Nq)]; }
                     else { Nt = next; Nv = nextv; }
                 }
