@@ -84,13 +84,7 @@ __global__ __launch_bounds__(64) void ewma_fit_kernel(EwmaFitArgs a) {
     const double* base = a.in + s0 * a.ld;
 
     EwmaOpt o;
-    o.pc = 0;
-    o.status = -1;
-    o.iter = 0;
-    o.evals = 0;
-    o.have_cur = 0;
-    o.cn = 0;
-    o.res_f = o.res_g = 0.0;
+    ewma_init(o);
     if (FIT) {
         if (live) ewma_advance(o);
     } else {
@@ -183,13 +177,7 @@ __global__ __launch_bounds__(64) void ewma_fit_res_kernel(EwmaFitArgs a) {
         for (int t = lane; t < T; t += 64) rows[r * kRow + t] = base[r * a.ld + t];
     __syncthreads();
     EwmaOpt o;
-    o.pc = 0;
-    o.status = -1;
-    o.iter = 0;
-    o.evals = 0;
-    o.have_cur = 0;
-    o.cn = 0;
-    o.res_f = o.res_g = 0.0;
+    ewma_init(o);
     if (live) ewma_advance(o);
     const double* myrow = rows + (live ? lane : 0) * kRow;
     bool first = true;

@@ -474,7 +474,7 @@ hipError_t launch_garch_fit(const GarchFitArgs& a0, bool fit, hipStream_t st) {
     const int budget = garch_pass_budget();
     void* scratch = nullptr;
     if (budget > 0) {
-        const int64_t cap = a.S;   // a slot per series (~650 B): every lane past its budget can park
+        const int64_t cap = a.S;   // a slot per series (sizeof(GarchOpt), 664 B): every lane past its budget can park
         const size_t state = (size_t)cap * sizeof(GarchOpt);
         hipError_t e = hipMallocAsync(&scratch, state + (size_t)cap * sizeof(int64_t) + 16, st);
         if (e != hipSuccess) return e;

@@ -26,8 +26,7 @@ int main() {
     for (long long s = 0; s < S; s++) {
         const double* ts = x.data() + s * T;
         sts::EwmaOpt o;
-        o.pc = 0; o.status = -1; o.iter = 0; o.evals = 0; o.have_cur = 0; o.cn = 0;
-        o.res_f = o.res_g = 0.0;
+        sts::ewma_init(o);
         sts::ewma_advance(o);
         long long passes = 0;
         while (o.status < 0) {

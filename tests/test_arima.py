@@ -235,7 +235,9 @@ def test_suite_stationarity_and_invertibility():
 
 MACHINE_CASES = [(1, 1, True, 250), (1, 1, True, 65), (1, 1, True, 24), (2, 2, True, 250), (2, 2, True, 65),
                  (0, 1, True, 65), (0, 1, True, 24), (3, 1, True, 250), (3, 1, True, 24), (0, 0, True, 65),
-                 (1, 2, False, 250), (1, 2, False, 24)]
+                 (1, 2, False, 250), (1, 2, False, 24),
+                 # the bracket's parabolic point lies between xB and xC and xB beats it; it beats neither
+                 (1, 1, False, 40), (0, 2, True, 12)]
 
 
 @pytest.mark.parametrize("p,q,icpt,T", MACHINE_CASES)

@@ -154,6 +154,10 @@ def check_machine(harness, x):
 
 def test_state_machine_matches_oracle(harness):
     check_machine(harness, garch_panel(12, 600, 100))
+    # short series whose bracket search leaves through the parabolic point between xB and xC:
+    # row 3 of the first because it beats fC, the second because xB beats it
+    check_machine(harness, garch_panel(4, 12, 0))
+    check_machine(harness, garch_panel(1, 20, 288))
 
 
 def test_state_machine_edge_series(harness):

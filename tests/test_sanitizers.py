@@ -4,7 +4,8 @@
 * the CPU oracle (oracle/sts_oracle.c, sts_oracle_garch.c) driven over every restated
   operator on edge shapes (tests/native/oracle_san_driver.c);
 * the device optimizer state machines compiled for the host (csrc/sts_ewma_opt.hpp,
-  csrc/sts_garch_opt.hpp through tests/native/*_sm_harness.cpp) on random, NaN, constant
+  csrc/sts_garch_opt.hpp, csrc/sts_arima_opt.hpp and the line search they share,
+  csrc/sts_cm_line.hpp, through tests/native/*_sm_harness.cpp) on random, NaN, constant
   and n = 1 series;
 * the C-ABI argument paths (csrc/sts_api.cpp, csrc/sts_host.cpp compiled for the host with
   the sanitizers, device objects linked as built): every invalid argument returns its
@@ -68,7 +69,14 @@ def _series_input(x):
     return "%d %d\n" % x.shape + " ".join("%x" % v for v in x.view(np.uint64).ravel())
 
 
-@pytest.mark.parametrize("which", ["ewma", "garch"])
+def _arima_input(p, q, icpt, x):
+    """arima_sm_harness's input: the series, then a start point of 0.1 per coefficient"""
+    init = np.full((x.shape[0], icpt + p + q), 0.1)
+    start = " ".join("%x" % v for v in init.view(np.uint64).ravel())
+    return "%d %d %d " % (p, q, icpt) + _series_input(x) + "\n" + start
+
+
+@pytest.mark.parametrize("which", ["ewma", "garch", "arima"])
 def test_state_machines_under_asan_ubsan(oracle_objs, tmp_path, which):
     gxx = need("g++")
     exe = str(tmp_path / ("%s_sm_san" % which))
@@ -82,11 +90,14 @@ def test_state_machines_under_asan_ubsan(oracle_objs, tmp_path, which):
     x[2] = 2.5                               # constant
     if which == "garch":
         x = x - x[:, :1]
-    r = subprocess.run([exe], input=_series_input(x), capture_output=True, text=True, env=ENV, timeout=600)
+    if which == "arima":                     # p = q = 1 with intercept; then n = 1: p = 1, q = 0, no intercept
+        many, single = _arima_input(1, 1, 1, x), _arima_input(1, 0, 0, x[:1])
+    else:
+        many, single = _series_input(x), _series_input(np.array([[0.3]]))
+    r = subprocess.run([exe], input=many, capture_output=True, text=True, env=ENV, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
     assert len(r.stdout.split("\n")) >= 4
-    one = subprocess.run([exe], input=_series_input(np.array([[0.3]])), capture_output=True, text=True, env=ENV,
-                         timeout=120)
+    one = subprocess.run([exe], input=single, capture_output=True, text=True, env=ENV, timeout=120)
     assert one.returncode == 0, one.stderr[-4000:]
 
 
