@@ -50,9 +50,6 @@ constexpr double kRuleLevel = 100.0;    // |mean| / |c| < 100
 // rule keeps a series AND 1 / pivot^2 < 4, the unrefined solution is within 8.8e-12
 // elementwise of the reference -- the reference's own distance to the exact solution there, the
 // refined one's too -- against 1.8e-9 without the pivot bound.
-#ifndef STS_AR_SKIP_REFINE
-#define STS_AR_SKIP_REFINE 1
-#endif
 constexpr double kRefineKappa = 4.0;
 
 // the intercept half of the rule on a finished fit
@@ -329,24 +326,17 @@ struct ArWaveLds {
     double tail[kRegPB];                     // Y(T-p .. T-1)
 };
 
-#ifndef STS_AR_FMA
-#define STS_AR_FMA 1   // explicit FMAs in the fit passes (A/B on C4: 6.26 -> 5.72 ms; remove stays bit-exact)
-#endif
-
-#ifndef STS_AR_DMA
-#define STS_AR_DMA 1   // series block in by LDS-DMA, residuals out through the same LDS block
-#endif
-
 #ifndef STS_AR_WAVES_PER_EU
 #define STS_AR_WAVES_PER_EU 2   // 256 VGPRs: the block (2B), windows and Gram rows stay spill-free
 #endif
-// DMA: the wave's series arrives by LDS-DMA (global_load_lds_dwordx4, 1 KB of consecutive
+// The wave's series arrives by LDS-DMA (global_load_lds_dwordx4, 1 KB of consecutive
 // steps per instruction, no VGPR staging) into a per-wave LDS block of 64 B doubles that is
 // exactly the lanes' blocks back to back; each lane then reads its B steps with 16-B LDS
 // reads.  The fit's LDS scratch (ArWaveLds) aliases that block once the series is in
 // registers, and the fused residuals go out through it again (16-B LDS writes at the lanes'
-// block offsets, then 1-KB coalesced stores).  Without DMA every load / store instruction
-// touches one 16-B piece per lane at a B * 8-byte stride: 64 cache lines per instruction.
+// block offsets, then 1-KB coalesced stores).  Without DMA (an unaligned row or odd T, the
+// runtime `dma` test) every load / store instruction touches one 16-B piece per lane at a
+// B * 8-byte stride: 64 cache lines per instruction.
 // The (p+1)^2 normal equations of the register kernels, solved UNIFORMLY: every lane of the
 // wave computes the same Gram, centring and Cholesky in its own registers (round 3).  The
 // round-2 form gave lane j row j and moved every column through v_readlane, LDS and a wave
@@ -425,19 +415,18 @@ __device__ __forceinline__ bool ar_normal_chol(const double (&Pd)[P + 1], double
     return ok;
 }
 
-template <int P, int B, int NWV = kRegWaves, bool DMA = false>
+template <int P, int B, int NWV = kRegWaves>
 __global__ __launch_bounds__(64 * NWV, STS_AR_WAVES_PER_EU) void ar_fit_blk_kernel(ArArgs a) {
     constexpr int BUFD = 64 * B;              // doubles per wave block
-    static_assert(!DMA || sizeof(ArWaveLds) <= BUFD * sizeof(double), "scratch fits the block");
-    __shared__ __attribute__((aligned(16))) double buf_mem[DMA ? NWV * BUFD : 2];
-    __shared__ ArWaveLds lds_mem[DMA ? 1 : NWV];
+    static_assert(sizeof(ArWaveLds) <= BUFD * sizeof(double), "scratch fits the block");
+    __shared__ __attribute__((aligned(16))) double buf_mem[NWV * BUFD];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // XCD x takes one contiguous range of series (C4: 4.039-4.049 vs 4.074 ms, profiles/r04_v10_ab_c4_xcd.jsonl)
     const int64_t s = xcd_remap(blockIdx.x, gridDim.x) * NWV + wave;
     if (s >= a.S) return;
-    double* buf = buf_mem + (DMA ? wave * BUFD : 0);
-    ArWaveLds& w = DMA ? *reinterpret_cast<ArWaveLds*>(buf) : lds_mem[wave];
+    double* buf = buf_mem + wave * BUFD;
+    ArWaveLds& w = *reinterpret_cast<ArWaveLds*>(buf);
     const int T = (int)a.T;
     const int t0 = lane * B;                  // this lane's block [t0, t0 + B)
     const double* xg = a.in + s * a.ld_in;
@@ -452,7 +441,7 @@ __global__ __launch_bounds__(64 * NWV, STS_AR_WAVES_PER_EU) void ar_fit_blk_kern
     const bool full = (t0 + B <= T);
     const bool al = ((reinterpret_cast<uintptr_t>(xg) & 15) == 0) && (B % 2 == 0);
     // DMA needs whole 16-B pieces inside the row: T even (and a 16-B aligned row)
-    const bool dma = DMA && al && !(T & 1);
+    const bool dma = al && !(T & 1);
     // head / tail of y straight from the DMA block instead of per-step LDS writes in the lag
     // pass (p <= 6: at p = 7, 8 the changed schedule spills)
     constexpr bool hd_blk = P <= 6;
@@ -523,17 +512,12 @@ __global__ __launch_bounds__(64 * NWV, STS_AR_WAVES_PER_EU) void ar_fit_blk_kern
         for (int j = 0; j < B; j++) {
             const double yj = Y(j);
             sy += yj;
-#if STS_AR_FMA
-            // the fit is a 1e-10-tolerance reduction, not a bit-exact path: explicit FMAs
-            // (the library is built with -ffp-contract=off for the bit-exact operators)
+            // the fit is a 1e-10-tolerance reduction, not a bit-exact path: explicit FMAs in the
+            // fit passes (the library is built with -ffp-contract=off for the bit-exact operators;
+            // C4 6.26 -> 5.72 ms; the remove pass stays bit-exact)
             Pd[0] = __builtin_fma(yj, yj, Pd[0]);
 #pragma unroll
             for (int d = 1; d <= P; d++) Pd[d] = __builtin_fma(yj, win[d], Pd[d]);
-#else
-            Pd[0] += yj * yj;
-#pragma unroll
-            for (int d = 1; d <= P; d++) Pd[d] += yj * win[d];
-#endif
 #pragma unroll
             for (int k = P; k >= 2; k--) win[k] = win[k - 1];
             win[1] = yj;
@@ -598,7 +582,7 @@ __global__ __launch_bounds__(64 * NWV, STS_AR_WAVES_PER_EU) void ar_fit_blk_kern
         for (int k = 1; k <= P; k++) sc -= phi[k] * cs[k];
         cpr = intercept ? sc * ifm : 0.0;
         AR_STAMP(3);
-        if (STS_AR_SKIP_REFINE && wellc && !illc) {
+        if (wellc && !illc) {
             // nearly orthogonal lags: the unrefined solution already sits at the reference's own
             // distance from the exact one (kRefineKappa); un-shift and skip the residual pass
             double sphi = 0.0;
@@ -624,23 +608,13 @@ __global__ __launch_bounds__(64 * NWV, STS_AR_WAVES_PER_EU) void ar_fit_blk_kern
             for (int j = 0; j < B; j++) {
                 const double yj = Y(j);
                 double e = yj - cpr;
-#if STS_AR_FMA
 #pragma unroll
                 for (int k = 1; k <= P; k++) e = __builtin_fma(-phi[k], win[k], e);
-#else
-#pragma unroll
-                for (int k = 1; k <= P; k++) e -= phi[k] * win[k];
-#endif
                 const int t = t0 + j;
                 e = (t >= P && t < T) ? e : 0.0;
                 g[0] += e;
-#if STS_AR_FMA
 #pragma unroll
                 for (int k = 1; k <= P; k++) g[k] = __builtin_fma(e, win[k], g[k]);
-#else
-#pragma unroll
-                for (int k = 1; k <= P; k++) g[k] += e * win[k];
-#endif
 #pragma unroll
                 for (int k = P; k >= 2; k--) win[k] = win[k - 1];
                 win[1] = yj;
@@ -846,11 +820,11 @@ static hipError_t launch_ar_fast(const ArArgs& a, hipStream_t st) {
 #define STS_AR_BLK(PP)                                                                          \
         case PP:                                                                                \
             switch (B) {                                                                        \
-            case 8: hipLaunchKernelGGL((ar_fit_blk_kernel<PP, 8, NWV, STS_AR_DMA>), g, b, 0, st, a); break;      \
-            case 16: hipLaunchKernelGGL((ar_fit_blk_kernel<PP, 16, NWV, STS_AR_DMA>), g, b, 0, st, a); break;    \
-            case 24: hipLaunchKernelGGL((ar_fit_blk_kernel<PP, 24, NWV, STS_AR_DMA>), g, b, 0, st, a); break;    \
-            case 32: hipLaunchKernelGGL((ar_fit_blk_kernel<PP, 32, NWV, STS_AR_DMA>), g, b, 0, st, a); break;    \
-            default: hipLaunchKernelGGL((ar_fit_blk_kernel<PP, 40, NWV, STS_AR_DMA>), g, b, 0, st, a); break;    \
+            case 8: hipLaunchKernelGGL((ar_fit_blk_kernel<PP, 8, NWV>), g, b, 0, st, a); break; \
+            case 16: hipLaunchKernelGGL((ar_fit_blk_kernel<PP, 16, NWV>), g, b, 0, st, a); break;\
+            case 24: hipLaunchKernelGGL((ar_fit_blk_kernel<PP, 24, NWV>), g, b, 0, st, a); break;\
+            case 32: hipLaunchKernelGGL((ar_fit_blk_kernel<PP, 32, NWV>), g, b, 0, st, a); break;\
+            default: hipLaunchKernelGGL((ar_fit_blk_kernel<PP, 40, NWV>), g, b, 0, st, a); break;\
             }                                                                                   \
             break;
         switch (a.p) {

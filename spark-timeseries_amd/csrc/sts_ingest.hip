@@ -16,10 +16,6 @@
 
 #include <hip/hip_runtime.h>
 
-#ifndef STS_WIRE_ROWS
-#define STS_WIRE_ROWS 1               // one wave per record for short series
-#endif
-
 namespace sts {
 namespace {
 
@@ -157,7 +153,7 @@ hipError_t per_series_grid(int64_t S, int64_t T, F&& launch) {
 hipError_t launch_wire_decode(const unsigned char* bytes, const int64_t* val_off, double* panel, int64_t S, int64_t T,
                               int64_t ld, hipStream_t st) {
     if (S <= 0 || T <= 0) return hipSuccess;
-    if (STS_WIRE_ROWS && T <= kRowT && (S + 3) / 4 <= 0x7fffffffLL) {
+    if (T <= kRowT && (S + 3) / 4 <= 0x7fffffffLL) {   // short series: one wave per record
         hipLaunchKernelGGL(wire_decode_rows_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, bytes, val_off,
                            panel, S, T, ld);
         return hipGetLastError();
@@ -170,7 +166,7 @@ hipError_t launch_wire_decode(const unsigned char* bytes, const int64_t* val_off
 hipError_t launch_wire_encode(const double* panel, int64_t S, int64_t T, int64_t ld, const int64_t* val_off,
                               unsigned char* bytes, hipStream_t st) {
     if (S <= 0 || T <= 0) return hipSuccess;
-    if (STS_WIRE_ROWS && T <= kRowT && (S + 3) / 4 <= 0x7fffffffLL) {
+    if (T <= kRowT && (S + 3) / 4 <= 0x7fffffffLL) {
         hipLaunchKernelGGL(wire_encode_rows_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, panel, S, T, ld,
                            val_off, bytes);
         return hipGetLastError();

@@ -17,103 +17,15 @@
 
 #include <hip/hip_runtime.h>
 
-#ifndef STS_TR16
-#define STS_TR16 1                    // 16-B transpose when shapes allow
-#endif
-#ifndef STS_TR_NT
-#define STS_TR_NT 1                   // non-temporal transpose stores (+2.5 %, r02_v10)
-#endif
-#ifndef STS_GATHER_BATCH
-#define STS_GATHER_BATCH 1            // instant gather: batched loads before the stores
-#endif
-#ifndef STS_TR_XCD
-#define STS_TR_XCD 1                  // transpose tiles XCD-contiguous (see transpose16_kernel)
-#endif
-#ifndef STS_NAN16
-#define STS_NAN16 1                   // 16-B NaN-instant scan when shapes allow
-#endif
-#ifndef STS_STATS_FAST
-#define STS_STATS_FAST 1              // seriesStats division off the step chain (see stats_fast_kernel)
-#endif
 #ifndef STS_STATS_CH
 #define STS_STATS_CH 16               // seriesStats chunk (steps staged per series)
-#endif
-#ifndef STS_STATS_LA
-#define STS_STATS_LA 1                // seriesStats chunks on 128-B line boundaries (stats_fast_kernel)
 #endif
 
 namespace sts {
 namespace {
 
 // java.lang.Math.max / min (what Scala's math.max / min call): NaN propagates, and
-// max(-0.0, 0.0) = 0.0, min(0.0, -0.0) = -0.0.
-__device__ __forceinline__ double jmax(double a, double b) {
-    if (a != a) return a;
-    if (a == 0.0 && b == 0.0 && __builtin_signbit(a)) return b;
-    return (a >= b) ? a : b;
-}
-__device__ __forceinline__ double jmin(double a, double b) {
-    if (a != a) return a;
-    if (a == 0.0 && b == 0.0 && __builtin_signbit(b)) return b;
-    return (a <= b) ? a : b;
-}
-
-// new StatCounter(series.valuesIterator) per series: out[s] = (mu, m2, max, min), n = T.
-template <int SPW, int CH>
-__global__ __launch_bounds__(64) void stats_kernel(const double* __restrict__ in, double* __restrict__ out,
-                                                   int64_t S, int64_t T, int64_t ld) {
-    constexpr int kRow = CH + 1;
-    constexpr int NLD = SPW * CH / 64;
-    __shared__ double tile[SPW * kRow];
-    const int lane = threadIdx.x;
-    const int64_t s0 = (int64_t)blockIdx.x * SPW;
-    const bool live = lane < SPW && s0 + lane < S;
-    const int ns = (S - s0 < SPW) ? (int)(S - s0) : SPW;
-    const double* base = in + s0 * ld;
-    double mu = 0.0, m2 = 0.0, mx = -__builtin_inf(), mn = __builtin_inf();
-    long long n = 0;
-    double pre[NLD];
-    auto fetch = [&](int64_t tc) {
-#pragma unroll
-        for (int i = 0; i < NLD; i++) {
-            const int row = (i * 64 + lane) / CH, col = (i * 64 + lane) % CH;
-            pre[i] = (row < ns && tc + col < T) ? base[row * ld + tc + col] : 0.0;
-        }
-    };
-    fetch(0);
-    for (int64_t tc = 0; tc < T; tc += CH) {
-        const int len = (T - tc < CH) ? (int)(T - tc) : CH;
-#pragma unroll
-        for (int i = 0; i < NLD; i++) {
-            const int row = (i * 64 + lane) / CH, col = (i * 64 + lane) % CH;
-            tile[row * kRow + col] = pre[i];
-        }
-        if (tc + CH < T) fetch(tc + CH);
-        __syncthreads();
-        if (live) {
-            const double* row = tile + lane * kRow;
-            for (int c = 0; c < len; c++) {
-                const double v = row[c];
-                const double delta = v - mu;         // StatCounter.merge(value)
-                n += 1;
-                mu += delta / (double)n;
-                m2 += delta * (v - mu);
-                mx = jmax(mx, v);
-                mn = jmin(mn, v);
-            }
-        }
-        __syncthreads();
-    }
-    if (live) {
-        double* o = out + (s0 + lane) * 4;
-        o[0] = mu;
-        o[1] = m2;
-        o[2] = mx;
-        o[3] = mn;
-    }
-}
-
-// Branch-free forms of jmax / jmin (same results, selects instead of early returns).
+// max(-0.0, 0.0) = 0.0, min(0.0, -0.0) = -0.0.  Branch-free: selects, no early returns.
 __device__ __forceinline__ double jmax_sel(double a, double b) {
     double r = (a >= b) ? a : b;
     r = (a == 0.0 && b == 0.0 && __builtin_signbit(a)) ? b : r;
@@ -125,7 +37,8 @@ __device__ __forceinline__ double jmin_sel(double a, double b) {
     return (a != a) ? a : r;
 }
 
-// The same StatCounter with the Welford division delta / n taken off the per-step chain.
+// new StatCounter(series.valuesIterator) per series: out[s] = (mu, m2, max, min), n = T, with
+// the Welford division delta / n taken off the per-step chain.
 // The compiler's IEEE f64 division is a Markstein sequence: y = 1/b refined by two Newton
 // steps from v_rcp_f64 (a function of b alone), q0 = a y, r = fma(-b, q0, a), q = fma(r, y,
 // q0), with v_div_scale / v_div_fmas / v_div_fixup scaling or patching only when the operands'
@@ -371,23 +284,19 @@ __global__ __launch_bounds__(64 * kGatherRows) void gather_instants_kernel(const
     const double* src = in + s * ld_in;
     double* dst = out + s * ld_out;
     const int lane = threadIdx.x & 63;
-    if (STS_GATHER_BATCH) {
-        // 8 loads in flight per lane before the stores (512 kept instants per pass)
-        for (int64_t j0 = 0; j0 < n_active; j0 += 512) {
-            double v[8];
+    // 8 loads in flight per lane before the stores (512 kept instants per pass)
+    for (int64_t j0 = 0; j0 < n_active; j0 += 512) {
+        double v[8];
 #pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int64_t j = j0 + lane + 64 * k;
-                v[k] = src[active[j < n_active ? j : n_active - 1]];
-            }
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int64_t j = j0 + lane + 64 * k;
-                if (j < n_active) dst[j] = v[k];
-            }
+        for (int k = 0; k < 8; k++) {
+            const int64_t j = j0 + lane + 64 * k;
+            v[k] = src[active[j < n_active ? j : n_active - 1]];
         }
-    } else {
-        for (int64_t j = lane; j < n_active; j += 64) dst[j] = src[active[j]];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int64_t j = j0 + lane + 64 * k;
+            if (j < n_active) dst[j] = v[k];
+        }
     }
 }
 
@@ -414,20 +323,15 @@ __global__ __launch_bounds__(256) void transpose_kernel(const double* __restrict
 // an odd pitch, so the column reads of the store phase spread over the banks.
 typedef double v2t __attribute__((ext_vector_type(2)));
 constexpr int kTrPitch = 64 + 1;
-// Tiles are XCD-contiguous (STS_TR_XCD): the instant tiles of one series block share the lines
+// Tiles are XCD-contiguous: the instant tiles of one series block share the lines
 // that straddle their boundaries (a 64-instant row segment of a 390-step row covers 5 lines for
 // 4), so they run on one XCD and its L2 serves the shared line once; dispatched round-robin over
 // the 8 XCDs (linear id x-fastest), the neighbours sat on different L2s and the panel was read
 // 1.25 x (profiles/r05_final_to_instants_traffic.json).
 __device__ __forceinline__ void tr_tile(int64_t& t0, int64_t& s0) {
-    int64_t bx = blockIdx.x, by = blockIdx.y;
-    if (STS_TR_XCD) {
-        const int64_t nx = gridDim.x, b = xcd_remap(bx + by * nx, nx * (int64_t)gridDim.y);
-        bx = b % nx;
-        by = b / nx;
-    }
-    t0 = bx * 64;
-    s0 = by * 64;
+    const int64_t nx = gridDim.x, b = xcd_remap(blockIdx.x + blockIdx.y * nx, nx * (int64_t)gridDim.y);
+    t0 = b % nx * 64;
+    s0 = b / nx * 64;
 }
 __global__ __launch_bounds__(256) void transpose16_kernel(const double* __restrict__ in, double* __restrict__ out,
                                                           int64_t S, int64_t T, int64_t ld_in, int64_t ld_out) {
@@ -454,8 +358,8 @@ __global__ __launch_bounds__(256) void transpose16_kernel(const double* __restri
         const int64_t t = t0 + tr, s = s0 + 2 * p;
         if (s < S && t < T) {
             const v2t o = {tile[tr * kTrPitch + 2 * p], tile[tr * kTrPitch + 2 * p + 1]};
-            if (STS_TR_NT) __builtin_nontemporal_store(o, reinterpret_cast<v2t*>(out + t * ld_out + s));
-            else *reinterpret_cast<v2t*>(out + t * ld_out + s) = o;
+            // non-temporal stores: +2.5 % (round 2, the r02_v10 profiles)
+            __builtin_nontemporal_store(o, reinterpret_cast<v2t*>(out + t * ld_out + s));
         }
     }
 }
@@ -465,12 +369,10 @@ __global__ __launch_bounds__(256) void transpose16_kernel(const double* __restri
 hipError_t launch_series_stats(const double* in, double* out, int64_t S, int64_t T, int64_t ld, hipStream_t st) {
     if (S <= 0) return hipSuccess;
     constexpr int SPW = 64, CH = STS_STATS_CH;   // A/B on 1M x 390: 1.00 ms vs 1.44 (32 x 64), 1.96 (16 x 64)
-    if (STS_STATS_FAST && T < (1LL << 52))
-        hipLaunchKernelGGL((stats_fast_kernel<SPW, CH, STS_STATS_LA != 0 && CH % 16 == 0>), dim3((unsigned)((S + SPW - 1) / SPW)), dim3(64), 0, st, in, out,
-                           S, T, ld);
-    else
-        hipLaunchKernelGGL((stats_kernel<SPW, CH>), dim3((unsigned)((S + SPW - 1) / SPW)), dim3(64), 0, st, in, out, S,
-                           T, ld);
+    // line-aligned chunks wherever a chunk row is whole 128-B lines (the shipped CH; a size variant
+    // with another CH takes the step-aligned form)
+    hipLaunchKernelGGL((stats_fast_kernel<SPW, CH, CH % 16 == 0>), dim3((unsigned)((S + SPW - 1) / SPW)), dim3(64), 0, st,
+                       in, out, S, T, ld);
     return hipGetLastError();
 }
 
@@ -485,7 +387,7 @@ hipError_t launch_nan_instants(const double* in, uint8_t* flags, int64_t S, int6
         }
         return hipSuccess;
     }
-    if (STS_NAN16 && T % 2 == 0 && ld % 2 == 0 && reinterpret_cast<uintptr_t>(in) % 16 == 0) {
+    if (T % 2 == 0 && ld % 2 == 0 && reinterpret_cast<uintptr_t>(in) % 16 == 0) {
         dim3 grid((unsigned)((T / 2 + kNanT - 1) / kNanT), (unsigned)gy);
         hipLaunchKernelGGL(nan_instants16_kernel, grid, dim3(kNanT), 0, st, in, flags, S, T, ld);
         return hipGetLastError();
@@ -520,7 +422,7 @@ hipError_t launch_gather_instants(const double* in, double* out, const int64_t* 
 hipError_t launch_transpose(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out,
                             hipStream_t st) {
     if (S <= 0 || T <= 0) return hipSuccess;
-    const bool v16 = STS_TR16 && (T % 2 == 0) && (S % 2 == 0) && (ld_in % 2 == 0) && (ld_out % 2 == 0) &&
+    const bool v16 = (T % 2 == 0) && (S % 2 == 0) && (ld_in % 2 == 0) && (ld_out % 2 == 0) &&
                      (reinterpret_cast<uintptr_t>(in) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0);
     for (int64_t s = 0; s < S; s += 64LL * 65535) {
         const int64_t n = (S - s < 64LL * 65535) ? S - s : 64LL * 65535;

@@ -1,5 +1,6 @@
 // sts_lanes.hpp -- cross-lane moves of doubles without the LDS crossbar, for the kernels whose
-// reductions / broadcasts sit on dependency chains (sts_ar.hip, sts_seg.hip), and the XCD remap.
+// reductions / broadcasts sit on dependency chains (sts_ar.hip, sts_seg.hip), the validity-word
+// helpers the tile and segment kernels share, and the XCD remap.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -69,6 +70,20 @@ __device__ __forceinline__ double suffix_sum_dpp(double v, int lane) {
     const double r3 = lane_bcast(v, 48), r2 = lane_bcast(v, 32) + r3, r1 = lane_bcast(v, 16) + r2;
     const int row = lane >> 4;
     return row == 3 ? v : v + (row == 2 ? r3 : row == 1 ? r2 : r1);
+}
+
+__device__ __forceinline__ bool isnan_d(double v) { return __builtin_isnan(v); }
+
+// Interleave two 32-step validity ballots into one 64-step word: bit i of ev -> bit 2i,
+// bit i of od -> bit 2i + 1.  s_bitreplicate_b64_b32 doubles every bit (i -> 2i, 2i + 1)
+// in one scalar op; the masks keep the even / odd copy.
+__device__ __forceinline__ unsigned long long bitrep(unsigned x) {
+    unsigned long long r;
+    asm("s_bitreplicate_b64_b32 %0, %1" : "=s"(r) : "s"(x));
+    return r;
+}
+__device__ __forceinline__ unsigned long long interleave2(unsigned ev, unsigned od) {
+    return (bitrep(ev) & 0x5555555555555555ull) | (bitrep(od) & 0xAAAAAAAAAAAAAAAAull);
 }
 
 // Bijective XCD-aware remap of a workgroup id (cdna_hip_programming.md §5 "XCD swizzle must be

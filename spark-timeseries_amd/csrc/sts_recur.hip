@@ -25,10 +25,6 @@
 #define STS_FDE_CH 128   // 8 x 128 1.42, 32 x 128 1.50-1.52, 32 x 64 1.59-1.67, 16 x 192 2.35, 16 x 256 2.24)
 #endif
 
-#ifndef STS_RECUR_V2
-#define STS_RECUR_V2 1   // 16-B global accesses in the C2 recurrence kernel (A/B: 1.673 vs 1.687 ms on C2)
-#endif
-
 namespace sts {
 namespace {
 
@@ -493,9 +489,10 @@ __global__ __launch_bounds__(256) void ar_naive_kernel(RecurArgs a) {
     }
 }
 
-// 16-B accesses need 16-B aligned rows (base and ld even)
+// 16-B accesses need 16-B aligned rows (base and ld even); against 8-B accesses on C2: 1.673 vs
+// 1.687 ms
 inline bool rows16(const RecurArgs& a) {
-    return STS_RECUR_V2 && ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.out)) & 15) == 0 &&
+    return ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.out)) & 15) == 0 &&
            a.ld_in % 2 == 0 && a.ld_out % 2 == 0;
 }
 

@@ -54,10 +54,6 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 // native vector (HIP's double2 is a struct: arrays of it are not promoted to registers)
 typedef double v2d __attribute__((ext_vector_type(2)));
 
-#ifndef STS_SEG_VTAB
-#define STS_SEG_VTAB 1                // word tables lane-parallel (DPP scans) instead of a scalar loop
-#endif
-
 constexpr int kW = 512;               // steps per tile
 constexpr int kWords = kW / 64;       // validity words per tile
 constexpr int kRing = 2 * kW + 128;   // two slots + a mirror of slot 0's head
@@ -78,8 +74,6 @@ struct WaveLds {
     int cN_pos, cN;                   // cache of the global look-ahead scan: first valid >= cN_pos is cN
 };
 
-__device__ __forceinline__ bool isnan_d(double v) { return __builtin_isnan(v); }
-
 // Order LDS traffic between lanes of ONE wave: LDS instructions of a wave execute in
 // order, so only the compiler has to be kept from reordering across the hand-off.
 // (LDS-only fences: a fence on all address spaces would also emit s_waitcnt vmcnt(0) and
@@ -88,16 +82,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
-
-__device__ __forceinline__ unsigned long long bitrep(unsigned x) {
-    unsigned long long r;
-    asm("s_bitreplicate_b64_b32 %0, %1" : "=s"(r) : "s"(x));
-    return r;
-}
-// bit i of ev -> bit 2i, bit i of od -> bit 2i + 1
-__device__ __forceinline__ unsigned long long interleave2(unsigned ev, unsigned od) {
-    return (bitrep(ev) & 0x5555555555555555ull) | (bitrep(od) & 0xAAAAAAAAAAAAAAAAull);
 }
 
 __device__ __forceinline__ double readlane_d(double v, int l) {
@@ -193,12 +177,6 @@ struct SegState {
     bool err;        // nearest: "Input is all NaNs!"
 };
 
-__device__ __forceinline__ unsigned long long uni64(unsigned long long v) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return ((unsigned long long)hi << 32) | lo;
-}
-
 // Validity masks of a tile held in registers -> LDS (word 2u: lanes 0..31 of register u,
 // word 2u + 1: lanes 32..63); returns the tile position of its first valid step (-1: none).
 __device__ __forceinline__ int masks_to_lds(const v2d (&R)[4], unsigned long long* dstm, int lane) {
@@ -231,9 +209,9 @@ __device__ __forceinline__ void impute_tile(WaveLds& w, const double* src, doubl
     const bool needN = (method == STS_FILL_LINEAR || method == STS_FILL_NEXT || method == STS_FILL_NEAREST);
     const int tend = (kb + kW < T) ? kb + kW : T;     // end of the real steps of this tile
     if (method != STS_FILL_NONE) {
-#if STS_SEG_VTAB
         // ---- word tables, lane-parallel: lane i < kWords owns word i (DPP scans within row 0,
-        //      v_readlane for the few values every lane needs) ----
+        //      v_readlane for the few values every lane needs) instead of a scalar loop over the
+        //      words ----
         const int wl = lane & (kWords - 1);
         const unsigned long long m = w.m2[SLOT][wl];
         const bool own_w = lane < kWords;
@@ -260,7 +238,9 @@ __device__ __forceinline__ void impute_tile(WaveLds& w, const double* src, doubl
         lnw = max(lnw, __builtin_amdgcn_update_dpp(-1, lnw, 0x112, 0xf, 0xf, false));
         lnw = max(lnw, __builtin_amdgcn_update_dpp(-1, lnw, 0x114, 0xf, 0xf, false));
         bool lg = false;   // linear: can a step lie more than kLongRun past its last valid index?
-        if (method == STS_FILL_LINEAR) {   // (conservative, as in sts_tile.hip)
+        if (method == STS_FILL_LINEAR) {   // (conservative, as in sts_tile.hip: a long run
+            // puts > kLongRun / 2 NaNs into one word, or reaches into the tile's first word
+            // from more than kLongRun before it)
             const int tz = m ? __ffsll(m) - 1 : 64;
             lg = __ballot(own_w && (__popcll(~m) > kLongRun / 2 ||
                                     (lane == 0 && tz > 0 && kb + tz - 1 - st.Lc > kLongRun))) != 0ull;
@@ -276,37 +256,6 @@ __device__ __forceinline__ void impute_tile(WaveLds& w, const double* src, doubl
         wb[kWords] = __builtin_amdgcn_readlane(incl, kWords - 1);
         const int run = __builtin_amdgcn_readlane(runw, kWords - 1);
         const int lastneed = __builtin_amdgcn_readlane(lnw, kWords - 1);
-#else
-        // ---- word tables (wave-uniform scalars, short-lived) ----
-        int wb[kWords + 1];
-        int run = st.Lc, lastneed = -1;
-        bool lg = false;   // linear: can a step lie more than kLongRun past its last valid index?
-        wb[0] = 0;
-#pragma unroll
-        for (int i = 0; i < kWords; i++) {
-            const unsigned long long m = uni64(w.m2[SLOT][i]);
-            if (method == STS_FILL_LINEAR) {   // (conservative, as in sts_tile.hip: a long run
-                // puts > kLongRun / 2 NaNs into one word, or reaches into the tile's first word
-                // from more than kLongRun before it)
-                const int tz = m ? __ffsll(m) - 1 : 64;
-                lg = lg || __popcll(~m) > kLongRun / 2 || (i == 0 && tz > 0 && kb + tz - 1 - run > kLongRun);
-            }
-            if (m) run = kb + 64 * i + 63 - __clzll(m);
-            const int hi = tend - (kb + 64 * i);               // real steps of word i: bits [0, hi)
-            unsigned long long r = 0ull;
-            if (hi > 0) {
-                r = ~m;
-                if (hi < 64) r &= (1ull << hi) - 1ull;
-            }
-            if (r) lastneed = kb + 64 * i + 63 - __clzll(r);
-            wb[i + 1] = wb[i] + __popcll(r);
-            if (lane == 0) {
-                w.need[i] = r;
-                w.lastUp[i] = run;
-                w.wbase[i] = wb[i];
-            }
-        }
-#endif
         const int lastv = (run >= kb) ? run : -1;     // last valid index in this tile
         const int nnan = wb[kWords];
         if (nnan > 0) {
@@ -329,21 +278,11 @@ __device__ __forceinline__ void impute_tile(WaveLds& w, const double* src, doubl
                         f = T;
                     }
                 }
-#if STS_SEG_VTAB
                 int fw = (own_w && m) ? gbase + __ffsll(m) - 1 : kBig;   // first valid in words >= wl
                 fw = min(fw, __builtin_amdgcn_update_dpp(kBig, fw, 0x101, 0xf, 0xf, false));
                 fw = min(fw, __builtin_amdgcn_update_dpp(kBig, fw, 0x102, 0xf, 0xf, false));
                 fw = min(fw, __builtin_amdgcn_update_dpp(kBig, fw, 0x104, 0xf, 0xf, false));
                 if (own_w) w.firstFrom[lane] = min(fw, f);
-#else
-                int ff = f;
-#pragma unroll
-                for (int i = kWords - 1; i >= 0; i--) {
-                    const unsigned long long m = uni64(w.m2[SLOT][i]);
-                    if (m) ff = kb + 64 * i + __ffsll(m) - 1;
-                    if (lane == 0) w.firstFrom[i] = ff;
-                }
-#endif
             }
             wave_sync();
             // ---- impute the compacted NaN positions; F goes into the ring in place

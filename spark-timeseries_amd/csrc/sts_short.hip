@@ -42,23 +42,10 @@ namespace {
 #endif
 constexpr int kShortWaves = STS_SHORT_WAVES;
 
-#ifndef STS_SHORT_TRIM
-#define STS_SHORT_TRIM 5   // fewer VALU per series (round 6): 1 = bounds as masks, a c0-filled tail;
-                           // 2 = + the middle sums under scalar lane masks, scalar-based DMA,
-                           // validity bits by add-with-carry; 3 = + the wave sums through LDS rows;
-                           // 4 = + rule 3's test on hardware reciprocals (acf_suspect_fast);
-                           // 5 = + the store pass's LDS reads batched
-#endif
-
-#ifndef STS_SHORT_COMPACT
-#define STS_SHORT_COMPACT 0   // the fill's in-block runs as one wave-wide list (A/B)
-#endif
-
-#ifndef STS_SHORT_DIAG
-#define STS_SHORT_DIAG 0   // timing-only cost models (tools/variant.sh): 1 no ACF, 2 no fill,
-                           // 3 no per-lag finalize, 4 no robust shift, 5 no lag products;
-                           // wrong results
-#endif
+// The one-wave kernel is trimmed for VALU count (round 6): the series bound as one
+// mask and a c0-filled tail instead of a test per step, the middle sums under scalar lane masks,
+// scalar-based DMA addresses, validity bits by add-with-carry, the wave sums through LDS rows,
+// rule 3's test on hardware reciprocals (acf_suspect_fast) and the store pass's LDS reads batched.
 
 // v in the lanes of the wave-uniform mask m, +0.0 elsewhere (v_cndmask on the SGPR pair: no
 // per-lane compare)
@@ -107,49 +94,30 @@ __device__ __forceinline__ unsigned long long short_load(double* buf, const doub
 #pragma unroll
     for (int i = 0; i < B / 2; i++) {
         const int u = 2 * (i * 64 + lane);
-        if (STS_SHORT_TRIM >= 2 && (i + 1) * 128 <= T)   // a whole piece: scalar base + the lane's 16 B, no VALU
+        if ((i + 1) * 128 <= T)   // a whole piece: scalar base + the lane's 16 B, no VALU
             glds16_s(src + i * 128, 16u * (unsigned)lane, lb + i * 1024);
         else   // past the series end: a copy of its last pair (T even), never read as data
-            glds16(src + (STS_SHORT_TRIM ? (u < T - 2 ? u : T - 2) : (u < T ? u : 0)), lb + i * 1024);
+            glds16(src + (u < T - 2 ? u : T - 2), lb + i * 1024);
     }
     dma_wait();
     wave_lds_sync();
-    unsigned long long vm = 0ull;
-    if (STS_SHORT_TRIM >= 2) {
-        // bits shifted in from the top step down: acc = 2 acc + (v ordered), one compare and one
-        // add-with-carry per step (the low word holds steps 0..31, the high word 32..B-1)
-        unsigned wlo = 0u, whi = 0u;
+    // bits shifted in from the top step down: acc = 2 acc + (v ordered), one compare and one
+    // add-with-carry per step (the low word holds steps 0..31, the high word 32..B-1)
+    unsigned wlo = 0u, whi = 0u;
 #pragma unroll
-        for (int j = B / 2 - 1; j >= 0; j--) {
-            const double2 v = *reinterpret_cast<const double2*>(buf + t0 + 2 * j);
-            if (2 * j >= 32) {
-                asm volatile("v_cmp_o_f64 vcc, %1, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(whi) : "v"(v.y) : "vcc");
-                asm volatile("v_cmp_o_f64 vcc, %1, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(whi) : "v"(v.x) : "vcc");
-            } else {
-                asm volatile("v_cmp_o_f64 vcc, %1, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(wlo) : "v"(v.y) : "vcc");
-                asm volatile("v_cmp_o_f64 vcc, %1, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(wlo) : "v"(v.x) : "vcc");
-            }
-        }
-        vm = ((unsigned long long)whi << 32) | wlo;
-        const int n = T - t0;   // steps of this block inside the series
-        vm &= n >= 64 ? ~0ull : n <= 0 ? 0ull : (1ull << n) - 1ull;
-    } else if (STS_SHORT_TRIM) {   // the bound as one mask instead of a test per step
-#pragma unroll
-        for (int j = 0; j < B / 2; j++) {
-            const double2 v = *reinterpret_cast<const double2*>(buf + t0 + 2 * j);
-            if (!__builtin_isnan(v.x)) vm |= 1ull << (2 * j);
-            if (!__builtin_isnan(v.y)) vm |= 1ull << (2 * j + 1);
-        }
-        const int n = T - t0;   // steps of this block inside the series
-        vm &= n >= 64 ? ~0ull : n <= 0 ? 0ull : (1ull << n) - 1ull;
-    } else {
-#pragma unroll
-        for (int j = 0; j < B / 2; j++) {
-            const double2 v = *reinterpret_cast<const double2*>(buf + t0 + 2 * j);
-            if (t0 + 2 * j < T && !__builtin_isnan(v.x)) vm |= 1ull << (2 * j);
-            if (t0 + 2 * j + 1 < T && !__builtin_isnan(v.y)) vm |= 1ull << (2 * j + 1);
+    for (int j = B / 2 - 1; j >= 0; j--) {
+        const double2 v = *reinterpret_cast<const double2*>(buf + t0 + 2 * j);
+        if (2 * j >= 32) {
+            asm volatile("v_cmp_o_f64 vcc, %1, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(whi) : "v"(v.y) : "vcc");
+            asm volatile("v_cmp_o_f64 vcc, %1, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(whi) : "v"(v.x) : "vcc");
+        } else {
+            asm volatile("v_cmp_o_f64 vcc, %1, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(wlo) : "v"(v.y) : "vcc");
+            asm volatile("v_cmp_o_f64 vcc, %1, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(wlo) : "v"(v.x) : "vcc");
         }
     }
+    unsigned long long vm = ((unsigned long long)whi << 32) | wlo;
+    const int n = T - t0;   // steps of this block inside the series: the bound as one mask
+    vm &= n >= 64 ? ~0ull : n <= 0 ? 0ull : (1ull << n) - 1ull;
     return vm;
 }
 
@@ -202,7 +170,7 @@ __device__ __forceinline__ bool short_fill(double* buf, unsigned long long vm, i
             }
         }
     };
-    if (STS_SHORT_DIAG != 2 && !all_nan) {
+    if (!all_nan) {
         // the block opens inside a run (or at a NaN at t = 0): its left end is Lc, its right
         // end the block's first valid step or Rc
         if (!(vf & 1ull) && t0 < T) {
@@ -213,48 +181,14 @@ __device__ __forceinline__ bool short_fill(double* buf, unsigned long long vm, i
         // runs that start inside the block: step t NaN, t - 1 valid
         const unsigned long long inT = (tend - t0 >= 64) ? ~0ull : ((1ull << (tend > t0 ? tend - t0 : 0)) - 1ull);
         unsigned long long rs = ~vf & (vf << 1) & inT;
-        if (STS_SHORT_COMPACT) {
-            // the wave's runs as one list, 64 at a time (a lane-by-lane loop runs as many rounds as
-            // the lane with the most runs): run g is the k-th run of the largest lane l with
-            // excl(l) <= g, excl = the runs of the lanes below (bit-sliced: nr <= B < 64)
-            const int nr = __popcll(rs);
-            int excl = 0, total = 0;
-#pragma unroll
-            for (int b = 0; b < 6; b++) {
-                const unsigned long long m = __ballot((nr >> b) & 1);
-                excl += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) << b;
-                total += __popcll(m) << b;
-            }
-            for (int base = 0; base < total; base += 64) {
-                const int g = base + lane;
-                int lo = 0;   // every lane searches (bpermute sources must be active)
-#pragma unroll
-                for (int st = 32; st >= 1; st >>= 1)
-                    if (__shfl(excl, lo + st) <= g) lo += st;
-                const int k = g - __shfl(excl, lo);
-                const unsigned long long rso = __shfl(rs, lo), vfo = __shfl(vf, lo);
-                const int Rco = __shfl(Rc, lo);
-                if (g < total) {
-                    unsigned long long m = rso;
-                    for (int i = 0; i < k; i++) m &= m - 1ull;
-                    const int j = __builtin_ctzll(m);
-                    const int to = lo * B;
-                    const int t = to + j;
-                    const int tendo = (to + B < T) ? to + B : T;
-                    const unsigned long long hi = (j + 1 < 64) ? vfo >> (j + 1) : 0ull;
-                    const int R = hi ? t + 1 + __builtin_ctzll(hi) : Rco;
-                    fill_run(t, R < tendo ? R : tendo, t - 1, R);
-                }
-            }
-        } else {
-            while (rs) {
-                const int j = __builtin_ctzll(rs);
-                rs &= rs - 1ull;
-                const int t = t0 + j;
-                const unsigned long long hi = (j + 1 < 64) ? vf >> (j + 1) : 0ull;
-                const int R = hi ? t + 1 + __builtin_ctzll(hi) : Rc;
-                fill_run(t, R < tend ? R : tend, t - 1, R);
-            }
+        // lane by lane (the runs as one wave-wide list of 64 at a time measured slower)
+        while (rs) {
+            const int j = __builtin_ctzll(rs);
+            rs &= rs - 1ull;
+            const int t = t0 + j;
+            const unsigned long long hi = (j + 1 < 64) ? vf >> (j + 1) : 0ull;
+            const int R = hi ? t + 1 + __builtin_ctzll(hi) : Rc;
+            fill_run(t, R < tend ? R : tend, t - 1, R);
         }
     }
     return all_nan;
@@ -263,24 +197,17 @@ __device__ __forceinline__ bool short_fill(double* buf, unsigned long long vm, i
 // the filled series out of the block: coalesced 1-KB stores
 template <int B>
 __device__ __forceinline__ void short_store(double* dst, const double* buf, int T, int lane) {
-    if (STS_SHORT_TRIM >= 5) {
-        // every piece read first (the block holds 64 B doubles: no bound on the reads), then the
-        // stores: one LDS wait instead of one per store behind its exec-masked branch
-        typedef double d2_t __attribute__((ext_vector_type(2)));
-        d2_t v[B / 2];
+    // every piece read first (the block holds 64 B doubles: no bound on the reads), then the
+    // stores: one LDS wait instead of one per store behind its exec-masked branch
+    typedef double d2_t __attribute__((ext_vector_type(2)));
+    d2_t v[B / 2];
 #pragma unroll
-        for (int i = 0; i < B / 2; i++) v[i] = *reinterpret_cast<const d2_t*>(buf + 2 * (i * 64 + lane));
-#pragma unroll
-        for (int i = 0; i < B / 2; i++) {
-            const int u = 2 * (i * 64 + lane);
-            if ((i + 1) * 128 <= T || u < T) __builtin_nontemporal_store(v[i], reinterpret_cast<d2_t*>(dst + u));
-        }
-        return;
-    }
+    for (int i = 0; i < B / 2; i++) v[i] = *reinterpret_cast<const d2_t*>(buf + 2 * (i * 64 + lane));
 #pragma unroll
     for (int i = 0; i < B / 2; i++) {
         const int u = 2 * (i * 64 + lane);
-        if (u < T) store_pair16<true>(dst + u, buf + u);   // nt stores: C1 0.0926 vs 0.1030 ms (nt loads too: 0.098)
+        // nt stores: C1 0.0926 vs 0.1030 ms (nt loads too: 0.098)
+        if ((i + 1) * 128 <= T || u < T) __builtin_nontemporal_store(v[i], reinterpret_cast<d2_t*>(dst + u));
     }
 }
 
@@ -306,8 +233,7 @@ __device__ __forceinline__ double short_finalize(double Pi, double Sm, double Qm
     const double v2 = sq2 - sum2 * sum2 / N;
     const double cv = Pi - sum1 * sum2 / N;
     const double r = cv / (__builtin_sqrt(v1) * __builtin_sqrt(v2));   // :89
-    suspect = STS_SHORT_TRIM >= 4 ? acf_suspect_fast(r, sum1, sq1, sum2, sq2, v1, v2, N, c0)
-                                  : acf_suspect(r, sum1, sq1, sum2, sq2, v1, v2, N, c0);
+    suspect = acf_suspect_fast(r, sum1, sq1, sum2, sq2, v1, v2, N, c0);
     return r;
 }
 
@@ -329,30 +255,21 @@ __global__ __launch_bounds__(64 * kShortWaves, 2) void short_fill_acf_kernel(Til
     if (a.out) short_store<B>(a.out + s * a.ld_out, buf, T, lane);
     if (a.err && lane == 0) a.err[s] = all_nan ? STS_ERR_ALL_NAN : STS_OK;
     const int K = a.K;
-    if (K <= 0 || a.acf_fused == nullptr || STS_SHORT_DIAG == 1) return;
+    if (K <= 0 || a.acf_fused == nullptr) return;
     // the ACF shift of the RAW series (sts_acf.hpp robust_shift) while the stores drain
-    const double c0 = (STS_SHORT_DIAG != 4) ? shift_from_masks<B>(buf, vm, T, lane, M == STS_FILL_PREVIOUS) : buf[0];
+    const double c0 = shift_from_masks<B>(buf, vm, T, lane, M == STS_FILL_PREVIOUS);
 
     // ---- ACF: y = F - c, lag products P_d = sum_t y_t y_{t-d}, middle sums ----
     double x[B];
-    if (STS_SHORT_TRIM) {
-        // the block past the series end holds c0, so y there is c0 - c0 = 0 without a select per
-        // step (a non-finite c0 makes every y NaN anyway)
-        for (int t = T + lane; t < BUFD; t += 64) buf[t] = c0;
-        wave_lds_sync();
+    // the block past the series end holds c0, so y there is c0 - c0 = 0 without a select per
+    // step (a non-finite c0 makes every y NaN anyway)
+    for (int t = T + lane; t < BUFD; t += 64) buf[t] = c0;
+    wave_lds_sync();
 #pragma unroll
-        for (int j = 0; j < B / 2; j++) {
-            const double2 v = *reinterpret_cast<const double2*>(buf + t0 + 2 * j);
-            x[2 * j] = v.x - c0;
-            x[2 * j + 1] = v.y - c0;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < B / 2; j++) {
-            const double2 v = *reinterpret_cast<const double2*>(buf + t0 + 2 * j);
-            x[2 * j] = (t0 + 2 * j < T) ? v.x - c0 : 0.0;
-            x[2 * j + 1] = (t0 + 2 * j + 1 < T) ? v.y - c0 : 0.0;
-        }
+    for (int j = 0; j < B / 2; j++) {
+        const double2 v = *reinterpret_cast<const double2*>(buf + t0 + 2 * j);
+        x[2 * j] = v.x - c0;
+        x[2 * j + 1] = v.y - c0;
     }
     // the head y(0..63) and the tail y(T-1-j), one per lane (T >= 128: disjoint)
     const double yh = buf[lane] - c0, zt = buf[T - 1 - lane] - c0;
@@ -372,27 +289,21 @@ __global__ __launch_bounds__(64 * kShortWaves, 2) void short_fill_acf_kernel(Til
 #pragma unroll
     for (int j = 0; j < B; j++) {
         const double yj = x[j];
-        if (STS_SHORT_TRIM >= 2) {
-            // rule 2's middle [kAcfEdge, T - kAcfEdge) holds step t0 + j for the lanes l in [lo, hi):
-            // a wave-uniform lane mask per j (scalar work), one masked copy of y for both sums, and
-            // two chains (even / odd j) for the latency
-            const int lo = j >= kAcfEdge ? 0 : (kAcfEdge - j + B - 1) / B;   // a constant after unrolling
-            const unsigned long long mm = (j <= mid_o ? mid_m1 : mid_m0) & ~((1ull << lo) - 1ull);
-            const double ym = lanes_keep(yj, mm);
-            if (j & 1) {
-                sm2 += ym;
-                qm2 = __builtin_fma(ym, ym, qm2);
-            } else {
-                sm += ym;
-                qm = __builtin_fma(ym, ym, qm);
-            }
-        } else if (acf_mid(t0 + j, T)) {
-            sm += yj;
-            qm = __builtin_fma(yj, yj, qm);
+        // rule 2's middle [kAcfEdge, T - kAcfEdge) holds step t0 + j for the lanes l in [lo, hi):
+        // a wave-uniform lane mask per j (scalar work), one masked copy of y for both sums, and
+        // two chains (even / odd j) for the latency
+        const int lo = j >= kAcfEdge ? 0 : (kAcfEdge - j + B - 1) / B;   // a constant after unrolling
+        const unsigned long long mm = (j <= mid_o ? mid_m1 : mid_m0) & ~((1ull << lo) - 1ull);
+        const double ym = lanes_keep(yj, mm);
+        if (j & 1) {
+            sm2 += ym;
+            qm2 = __builtin_fma(ym, ym, qm2);
+        } else {
+            sm += ym;
+            qm = __builtin_fma(ym, ym, qm);
         }
 #pragma unroll
-        for (int d = 1; d <= KM; d++)
-            if (STS_SHORT_DIAG != 5) P[d] = __builtin_fma(yj, win[d], P[d]);
+        for (int d = 1; d <= KM; d++) P[d] = __builtin_fma(yj, win[d], P[d]);
 #pragma unroll
         for (int k = KM; k >= 2; k--) win[k] = win[k - 1];
         win[1] = yj;
@@ -401,17 +312,16 @@ __global__ __launch_bounds__(64 * kShortWaves, 2) void short_fill_acf_kernel(Til
     //      (lane d - 1 collects lag d), added in wave_sum_dpp's order ----
     wave_lds_sync();   // every read of the filled block is done: it becomes scratch
     double* scr = buf;
-    if (STS_SHORT_TRIM >= 2) {
-        sm += sm2;
-        qm += qm2;
-    }
+    sm += sm2;
+    qm += qm2;
     double Pi, Sm, Qm;
     // the V = KM + 2 quantities (0: sm, d: P_d, KM + 1: qm) of every lane as LDS rows of RS
     // doubles (RS odd: conflict-free writes), then lane (v, q) sums quantity v over the q-th of
     // G lane groups and a second pass adds the G partials -- ~V + G adds per lane where the DPP
-    // row sums cost 12 VALU per quantity (round 6)
+    // row sums cost 12 VALU per quantity (round 6); an instantiation whose block cannot hold the
+    // rows keeps the DPP row sums
     constexpr int V = KM + 2, RS = V | 1, G = 64 / V, LG = (64 + G - 1) / G;
-    if (STS_SHORT_TRIM >= 3 && 64 * RS + G * V <= BUFD) {
+    if (64 * RS + G * V <= BUFD) {
 #pragma unroll
         for (int v = 0; v < V; v++) scr[lane * RS + v] = v == 0 ? sm : v == KM + 1 ? qm : P[v];
         wave_lds_sync();
@@ -462,10 +372,6 @@ __global__ __launch_bounds__(64 * kShortWaves, 2) void short_fill_acf_kernel(Til
         Sm = (sr.x + sr.y) + (sr.z + sr.w);
         Qm = (qr.x + qr.y) + (qr.z + qr.w);
     }
-    if (STS_SHORT_DIAG == 3) {
-        if (lane < K) a.acf_fused[s * K + lane] = Pi + Sm + Qm;
-        return;
-    }
     bool sus;
     double r = short_finalize(Pi, Sm, Qm, yh, zt, c0, T, lane, sus);
     // sts_acf.hpp rule 3: a suspect series takes the reference's loop over the filled series
@@ -515,7 +421,6 @@ __global__ __launch_bounds__(128, 4) void short_pair_kernel(TileArgs a) {
     const int64_t G = gridDim.x, g = blockIdx.x;
     const int64_t nslots = g < a.S ? (a.S - g + G - 1) / G : 0;
     const int T = (int)a.T;
-    const int t0 = lane * B;
     const int K = a.K;
     const bool acf = K > 0 && a.acf_fused != nullptr;
     static_assert(KM <= B, "the lag partners reach one lane back only");
@@ -550,7 +455,7 @@ __global__ __launch_bounds__(128, 4) void short_pair_kernel(TileArgs a) {
             }
             yh = buf[lane] - c0;
             zt = buf[T - 1 - lane] - c0;
-        } else if (p >= 1 && acf && STS_SHORT_DIAG != 1) {   // ---- the other wave: slot p - 1's ACF from registers ----
+        } else if (p >= 1 && acf) {   // ---- the other wave: slot p - 1's ACF from registers ----
             const int64_t s = g + (p - 1) * G;
             constexpr int NP = (KM + kPairLags - 1) / kPairLags, LP = (KM + NP - 1) / NP;
             double Pi = 0.0, sm = 0.0, qm = 0.0;
@@ -576,7 +481,7 @@ __global__ __launch_bounds__(128, 4) void short_pair_kernel(TileArgs a) {
                     }
 #pragma unroll
                     for (int q = 0; q < LP; q++)
-                        if (j >= d0 + q && d0 + q <= KM && STS_SHORT_DIAG != 5) P[q] = __builtin_fma(x[j], x[j - d0 - q], P[q]);
+                        if (j >= d0 + q && d0 + q <= KM) P[q] = __builtin_fma(x[j], x[j - d0 - q], P[q]);
                 }
                 // wave sums into lane 63 (DPP only), then lag d's to lane d - 1
 #pragma unroll

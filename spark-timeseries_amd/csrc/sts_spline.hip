@@ -147,10 +147,6 @@ __global__ __launch_bounds__(kBlock) void spline_fill_kernel(const double* __res
     }
 }
 
-#ifndef STS_SPLINE_LDS
-#define STS_SPLINE_LDS 1   // round 6: the rows' reads and the (mu, z) scratch through LDS (below)
-#endif
-
 // Round 6: the same two sweeps, the same arithmetic in the same order (bit-identical), with the
 // memory access reorganised.  spline_fill_kernel's lanes read their own rows 8 B at a time --
 // each load instruction touches 64 cache lines, one per lane -- and that, not the FP64 chain,
@@ -381,7 +377,7 @@ hipError_t launch_spline(const double* in, double* out, int64_t S, int64_t T, in
     if (S <= 0 || T <= 0) return hipSuccess;
     for (int64_t s0 = 0; s0 < S; s0 += batch) {
         const int64_t n = S - s0 < batch ? S - s0 : batch;
-        if (STS_SPLINE_LDS && !(ld_in & 1) && !(ld_out & 1) && !(reinterpret_cast<uintptr_t>(in) & 15) &&
+        if (!(ld_in & 1) && !(ld_out & 1) && !(reinterpret_cast<uintptr_t>(in) & 15) &&
             !(reinterpret_cast<uintptr_t>(out) & 15) && T < (int64_t(1) << 30)) {   // 16-B row pieces, 32-bit steps
             dim3 g((unsigned)((n + 63) / 64)), b(64);
             hipLaunchKernelGGL(spline_lds_kernel, g, b, 0, st, in + s0 * ld_in, out + s0 * ld_out,

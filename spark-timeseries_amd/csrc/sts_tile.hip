@@ -74,8 +74,6 @@ typedef int i4v __attribute__((ext_vector_type(4)));      // 16-B reads of the w
 constexpr int kThreads = 256;
 constexpr int kBig = 1 << 30;
 
-__device__ __forceinline__ bool isnan_d(double v) { return __builtin_isnan(v); }
-
 // Diagnostic build only (-DSTS_STAMPS, `make stamps`): per-phase s_memtime accumulation,
 // summed over waves into a device array read back by sts_debug_stamps().  The shipped
 // library has no stamps.
@@ -92,18 +90,6 @@ __device__ unsigned long long g_stamps[16];
     do {         \
     } while (0)
 #endif
-
-// Interleave two 32-step validity ballots into one 64-step word: bit i of ev -> bit 2i,
-// bit i of od -> bit 2i + 1.  s_bitreplicate_b64_b32 doubles every bit (i -> 2i, 2i + 1)
-// in one scalar op; the masks keep the even / odd copy.
-__device__ __forceinline__ unsigned long long bitrep(unsigned x) {
-    unsigned long long r;
-    asm("s_bitreplicate_b64_b32 %0, %1" : "=s"(r) : "s"(x));
-    return r;
-}
-__device__ __forceinline__ unsigned long long interleave2(unsigned ev, unsigned od) {
-    return (bitrep(ev) & 0x5555555555555555ull) | (bitrep(od) & 0xAAAAAAAAAAAAAAAAull);
-}
 
 // An opaque copy of a per-lane value: computed where it is used, per tile, instead of being
 // hoisted out of the tile loop by LICM and kept live in a VGPR for the whole kernel (round 3:
