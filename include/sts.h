@@ -32,6 +32,11 @@
  *   - Any 8-byte-aligned base and any ld >= T are accepted.  A 16-byte-aligned base with
  *     even ld (and, for some kernels, even T) only selects faster load / store forms; the
  *     result is held to the same bar in every layout.
+ *   - A FACTOR PANEL (t5 / t6) is held to the same contract row by row: factor j of series s
+ *     is the T elements at factors[s*fs + j*ld_f + t]; results depend only on those elements,
+ *     no entry point writes to a factor panel, any 8-byte-aligned base, any ld_f >= T and any
+ *     fs that does not overlap are accepted, and the device entry points read nothing outside
+ *     the T elements of each factor row (tests/test_bgbp_gpu.py).
  *
  * Memory: functions without a `_host` suffix take DEVICE pointers (HBM,
  * e.g. hipMalloc'd) and are stream-ordered on `stream` (a hipStream_t; NULL
@@ -387,8 +392,7 @@ int sts_ar_fit_remove(const double* in, double* out, int64_t S, int64_t T, int64
 /* ---- t1-t4: TimeSeriesStatisticalTests (S/stats/TimeSeriesStatisticalTests.scala), one scalar
  * statistic per series of a panel.  stat (and pvalue, which may be NULL) are device arrays of S
  * doubles; the input is never written; stream-ordered.  A series holding any NaN gets a NaN
- * statistic (and p-value) with status 0.  bgtest / bptest take a per-series factor matrix and
- * are not part of this ABI. */
+ * statistic (and p-value) with status 0. */
 typedef enum sts_regression {
     STS_REG_NC = 0,   /* no constant                 */
     STS_REG_C = 1,    /* constant                    */
@@ -434,6 +438,48 @@ int sts_dw_test(const double* in, int64_t S, int64_t T, int64_t ld, double* stat
  * ChiSquaredDistribution.cumulativeProbability), formed as one minus the CDF like the reference. */
 int sts_lb_test(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag, double* stat,
                 double* pvalue, void* stream);
+
+/* ---- t5 / t6: bptest(residuals, factors) (:311-319) and bgtest(residuals, factors, maxLag)
+ * (:266-278), the two tests that take the factors of the regression the residuals came from.
+ *
+ * Factor panel: a factor is a series.  Factor j (0 <= j < k) of series s at time t is
+ * factors[s*fs + j*ld_f + t], ld_f >= T, 8-byte-aligned base, never written.  fs == 0: ONE factor
+ * matrix shared by the whole panel (a handful of market factors, the common case); fs != 0:
+ * per-series factors, fs >= (k - 1)*ld_f + T.  A Breeze DenseMatrix(T, k) is column-major, so its
+ * `data` array IS this layout with ld_f = T; no JNI symbols are added.
+ *
+ * Both follow commons-math3 3.4.1 OLSMultipleLinearRegression with intercept, R^2 = 1 - RSS / TSS
+ * with TSS the centred second moment (calculateRSquared):
+ *   bptest: response e[t]^2, t = 0..T-1; regressors 1, F_0..F_{k-1} (:312-315);
+ *           stat = T R^2 (:316), pvalue = 1 - chi2cdf(stat, k) (:317-318).
+ *   bgtest: nObs = T - maxLag; response e[maxLag..T); regressors 1, the factors' rows maxLag..T
+ *           and e[t-1]..e[t-maxLag] (lagMatTrimBoth(residuals, maxLag, false), :270-275, which DROPS
+ *           the first maxLag rows where R's lmtest zero-fills them); stat = nObs R^2 (:276),
+ *           pvalue = 1 - chi2cdf(stat, maxLag) (:277).
+ * R^2 is computed as the explained sum of squares over TSS, through an orthonormal basis of the
+ * centred factors and (bgtest) a Cholesky factor of the residualised lags' Gram matrix: 1e-10
+ * relative to the reference on ordinary inputs (statistical tests).  p-values are formed
+ * as one minus the CDF, as t4's.  Results do not depend on S, on neighbouring series or on whether
+ * the factors are shared.
+ *
+ * 1 <= k <= 8 (STS_MAX_FACTORS) and 1 <= maxLag <= 31, else STS_ERR_BAD_ARG; ld < T, ld_f < T or
+ * 0 < fs < (k - 1)*ld_f + T (or fs < 0) -> STS_ERR_BAD_ARG.  Observations <= columns (T <= 1 + k;
+ * nObs <= 1 + k + maxLag) -> STS_ERR_NOT_ENOUGH_DATA (parity note: the reference throws below
+ * equality only and returns noise at equality).  Call-level errors leave the outputs untouched.
+ * Per series: any NaN among the values its regression reads (its residuals, its factors' rows
+ * used) -> NaN statistic and p-value, status 0; a bit-constant response (all e[t]^2 equal; all
+ * e[maxLag..T) equal) -> NaN, status 0 (the reference's 0 / 0); a rank-deficient design (a factor
+ * that is constant over the rows used, a duplicated factor: a column whose remainder after
+ * projection on the earlier ones is below 2^-40 of its centred norm, i.e. rounding noise; or a
+ * zero pivot among the residualised lags) -> STS_ERR_SINGULAR in err_per_series and NaN.  pvalue
+ * and err_per_series may be NULL as in sts_adf_test. */
+#define STS_MAX_FACTORS 8
+int sts_bp_test(const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k,
+                int64_t ld_f, int64_t fs, double* stat, double* pvalue, int32_t* err_per_series,
+                void* stream);
+int sts_bg_test(const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k,
+                int64_t ld_f, int64_t fs, int max_lag, double* stat, double* pvalue,
+                int32_t* err_per_series, void* stream);
 
 /* ---- synthetic panels: counter-based Philox4x32-10, bit-identical
  * to the CPU generator in oracle/, so any shard can be regenerated anywhere. ---- */
@@ -516,6 +562,15 @@ int sts_kpss_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int r
 int sts_dw_test_host(const double* in, int64_t S, int64_t T, int64_t ld, double* stat);
 int sts_lb_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag, double* stat,
                      double* pvalue);
+/* t5 / t6: resid and factors are both host arrays.  A shared factor matrix (fs == 0) is copied
+ * to the device once; per-series factors ride the staging pipeline as one block of
+ * (k - 1)*ld_f + T doubles per series. */
+int sts_bp_test_host(const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors,
+                     int k, int64_t ld_f, int64_t fs, double* stat, double* pvalue,
+                     int32_t* err_per_series);
+int sts_bg_test_host(const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors,
+                     int k, int64_t ld_f, int64_t fs, int max_lag, double* stat, double* pvalue,
+                     int32_t* err_per_series);
 
 #ifdef __cplusplus
 }

@@ -1491,6 +1491,77 @@ int sts_lb_test(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag,
     return STS_OK;
 }
 
+// bgtest / bptest: the factors' orthonormal basis goes to a stream-ordered scratch (one for shared
+// factors; per-series factors in chunks of series whose bases fit kBasisChunkBytes, so the scratch
+// stays bounded and warm in the caches), then one workgroup per series
+constexpr size_t kBasisChunkBytes = (size_t)256 << 20;
+
+static int bgbp_test(bool bp, const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k,
+                     int64_t ld_f, int64_t fs, int max_lag, double* stat, double* pvalue, int32_t* err_per_series,
+                     void* stream) {
+    const char* name = bp ? "bptest" : "bgtest";
+    int r;
+    if (k < 1 || k > sts::kMaxFactors)
+        return fail(STS_ERR_BAD_ARG, "%s: %d factors outside [1, %d]", name, k, sts::kMaxFactors);
+    if (!bp && (max_lag < 1 || max_lag > 31)) return fail(STS_ERR_BAD_ARG, "bgtest: maxLag %d outside [1, 31]", max_lag);
+    if ((r = stat_panel(resid, S, T, ld, stat, name))) return r;
+    if (ld_f < T)
+        return fail(STS_ERR_BAD_ARG, "%s: factor leading dimension %lld < T=%lld", name, (long long)ld_f, (long long)T);
+    if (fs != 0 && fs < (int64_t)(k - 1) * ld_f + T)
+        return fail(STS_ERR_BAD_ARG, "%s: factor series stride %lld overlaps (needs 0 or >= %lld)", name, (long long)fs,
+                    (long long)((int64_t)(k - 1) * ld_f + T));
+    if (S * T > 0 && !factors) return fail(STS_ERR_BAD_ARG, "%s: null factor pointer", name);
+    const int L = bp ? 0 : max_lag;
+    const int64_t n_obs = T - L, cols = 1 + (int64_t)k + L;
+    if (n_obs <= cols)
+        return fail(STS_ERR_NOT_ENOUGH_DATA, "%s: not enough data (%lld rows) for the number of predictors (%lld)", name,
+                    (long long)n_obs, (long long)cols);
+    if (S == 0) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    ErrSink es(err_per_series, S, st);
+    if ((r = es.prepare())) return r;
+    sts::BgBpArgs a{};
+    a.in = resid; a.S = S; a.T = T; a.ld = ld; a.factors = factors; a.ld_f = ld_f; a.fs = fs; a.k = k; a.L = L;
+    a.squares = bp; a.lo = L; a.n = n_obs; a.stat = stat; a.err = es.dev;
+    // scratch bases: one for shared factors, a chunk's worth for per-series factors -- none where the
+    // kernels build each series' basis in LDS (one chunk, then)
+    const bool own = sts::own_basis(a);
+    const size_t per_basis = (size_t)k * (size_t)n_obs * sizeof(double);
+    int64_t chunk = 1;
+    if (own) chunk = S;
+    else if (fs != 0) chunk = std::max<int64_t>(1, std::min<int64_t>(S, (int64_t)(kBasisChunkBytes / per_basis)));
+    Scratch sc(st);
+    const size_t nbasis = own ? 0 : (size_t)chunk;
+    HIP_TRY(sc.alloc(per_basis * nbasis + nbasis * sizeof(int32_t)), "hipMallocAsync(factor basis)");
+    a.basis = static_cast<double*>(sc.p);
+    a.info = reinterpret_cast<int32_t*>(a.basis + (size_t)k * (size_t)n_obs * nbasis);
+    if (fs == 0) {
+        HIP_TRY(sts::launch_factor_basis(a, 0, 1, st), name);
+        HIP_TRY(timed(st, [&] { return sts::launch_bgbp(a, 0, S, st); }), name);
+    } else {
+        a.basis_stride = (int64_t)k * n_obs;
+        a.info_stride = 1;
+        for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+            const int64_t ns = std::min<int64_t>(chunk, S - s0);
+            HIP_TRY(sts::launch_factor_basis(a, s0, ns, st), name);
+            HIP_TRY(timed(st, [&] { return sts::launch_bgbp(a, s0, ns, st); }), name);
+        }
+    }
+    if (pvalue) HIP_TRY(sts::launch_chi2_pvalue(stat, pvalue, S, bp ? k : L, st), name);
+    return es.finish(name);
+}
+
+int sts_bp_test(const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k, int64_t ld_f,
+                int64_t fs, double* stat, double* pvalue, int32_t* err_per_series, void* stream) {
+    return bgbp_test(true, resid, S, T, ld, factors, k, ld_f, fs, 0, stat, pvalue, err_per_series, stream);
+}
+
+int sts_bg_test(const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k, int64_t ld_f,
+                int64_t fs, int max_lag, double* stat, double* pvalue, int32_t* err_per_series, void* stream) {
+    return bgbp_test(false, resid, S, T, ld, factors, k, ld_f, fs, max_lag, stat, pvalue, err_per_series, stream);
+}
+
 int sts_gen_panel(double* out, int64_t s0, int64_t S, int64_t T, int64_t ld, uint64_t seed, double nan_p,
                   void* stream) {
     int r;

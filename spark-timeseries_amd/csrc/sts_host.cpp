@@ -727,4 +727,66 @@ int sts_lb_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int max
                   });
 }
 
+// bgtest / bptest: a shared factor matrix (fs == 0) is copied to the device once, row by row (only
+// the T elements of each factor row are read), and every chunk of residuals runs against it;
+// per-series factors ride the staging pipeline as one block of (k - 1) * ld_f + T doubles per series
+// (the padding between a series' own factor rows is moved with it and never used).
+static int bgbp_host(bool bp, const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k,
+                     int64_t ld_f, int64_t fs, int max_lag, double* stat, double* pvalue, int32_t* err) {
+    auto dev_call = [&](const double* e, int64_t n, int64_t lde, const double* f, int64_t ldf, int64_t fsf, double* st,
+                        double* pv, int32_t* er, hipStream_t s) {
+        return bp ? sts_bp_test(e, n, T, lde, f, k, ldf, fsf, st, pv, er, s)
+                  : sts_bg_test(e, n, T, lde, f, k, ldf, fsf, max_lag, st, pv, er, s);
+    };
+    // every argument error first, on the caller's shapes: nothing is staged or copied on bad input
+    int r = sts::validate([&] { return dev_call(resid, S, ld, factors, ld_f, fs, stat, pvalue, nullptr, nullptr); });
+    if (r) return r;
+    if (S <= 0) return STS_OK;
+    const size_t row = (size_t)T * sizeof(double);
+    ErrOut eo(err, S);
+    int st;
+    if (fs == 0) {
+        void* df = nullptr;
+        hipError_t e = hipMalloc(&df, (size_t)k * row);
+        if (e != hipSuccess) return hip_status(e, "hipMalloc(factors)");
+        e = hipMemcpy2D(df, row, factors, (size_t)ld_f * sizeof(double), row, (size_t)k, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(df);
+            return hip_status(e, "hipMemcpy2D(factors)");
+        }
+        st = staged(S, {in_arg(resid, row, panel_stride(ld)), out_arg(stat, sizeof(double), sizeof(double)),
+                        out_arg(pvalue, sizeof(double), sizeof(double)), out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
+                    [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
+                        if (!s) return (int)STS_OK;   // validated above (the factors are on the device by now)
+                        return dev_call(static_cast<const double*>(d[0]), n, T, static_cast<const double*>(df), T, 0,
+                                        static_cast<double*>(d[1]), pvalue ? static_cast<double*>(d[2]) : nullptr,
+                                        static_cast<int32_t*>(d[3]), s);
+                    });
+        (void)hipFree(df);   // every chunk is back
+    } else {
+        const int64_t span = (int64_t)(k - 1) * ld_f + T;
+        st = staged(S, {in_arg(resid, row, panel_stride(ld)),
+                        in_arg(factors, (size_t)span * sizeof(double), (size_t)fs * sizeof(double)),
+                        out_arg(stat, sizeof(double), sizeof(double)), out_arg(pvalue, sizeof(double), sizeof(double)),
+                        out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
+                    [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
+                        if (!s) return (int)STS_OK;
+                        return dev_call(static_cast<const double*>(d[0]), n, T, static_cast<const double*>(d[1]), ld_f,
+                                        span, static_cast<double*>(d[2]), pvalue ? static_cast<double*>(d[3]) : nullptr,
+                                        static_cast<int32_t*>(d[4]), s);
+                    });
+    }
+    return eo.finish(st, S, bp ? "bptest" : "bgtest");
+}
+
+int sts_bp_test_host(const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k, int64_t ld_f,
+                     int64_t fs, double* stat, double* pvalue, int32_t* err) {
+    return bgbp_host(true, resid, S, T, ld, factors, k, ld_f, fs, 0, stat, pvalue, err);
+}
+
+int sts_bg_test_host(const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k, int64_t ld_f,
+                     int64_t fs, int max_lag, double* stat, double* pvalue, int32_t* err) {
+    return bgbp_host(false, resid, S, T, ld, factors, k, ld_f, fs, max_lag, stat, pvalue, err);
+}
+
 }  // extern "C"

@@ -281,6 +281,33 @@ hipError_t launch_adf(const StatArgs& a, hipStream_t st);
 hipError_t launch_adf_pvalue(const double* stat, double* pv, int64_t S, int regression, hipStream_t st);
 // Ljung-Box statistic (and p-value unless pv is null) from an S x K ACF
 hipError_t launch_lb(const double* acf, int64_t S, int64_t T, int K, double* stat, double* pv, hipStream_t st);
+// Breusch-Godfrey / Breusch-Pagan.  kMaxFactors bounds k: the kernels keep one accumulator and one
+// basis value per factor in registers (unrolled to this bound) and an LDS row of it per lag window.
+constexpr int kMaxFactors = STS_MAX_FACTORS;
+struct BgBpArgs {
+    const double* in;        // residual panel
+    int64_t S, T, ld;
+    const double* factors;   // factor j of series s at factors[s * fs + j * ld_f + t]; fs == 0: shared
+    int64_t ld_f, fs;
+    int k;                   // factors, 1..kMaxFactors
+    int L;                   // BG: maxLag; BP: 0
+    bool squares;            // BP: the response is e^2
+    int64_t lo, n;           // rows lo .. lo + n of the factors are used (lo = L, n = T - L)
+    double* basis;           // scratch: k x n per basis, basis b at basis + b * basis_stride
+    int64_t basis_stride;    // 0: one basis for every series
+    int32_t* info;           // scratch: per basis 0 or STS_ERR_SINGULAR
+    int64_t info_stride;     // 0 or 1
+    double* stat;            // S
+    int32_t* err;            // per-series status, zeroed by the caller
+};
+// true when launch_bgbp's kernels build each series' basis in LDS themselves (per-series factors of
+// short series): launch_factor_basis is then a no-op and basis / info are not used
+bool own_basis(const BgBpArgs& a);
+// bases of series s0 .. s0 + nb (nb = 1 and s0 = 0 for shared factors) into a.basis / a.info
+hipError_t launch_factor_basis(const BgBpArgs& a, int64_t s0, int64_t nb, hipStream_t st);
+// statistics of series s0 .. s0 + ns; basis / info are indexed from the chunk's first series
+hipError_t launch_bgbp(const BgBpArgs& a, int64_t s0, int64_t ns, hipStream_t st);
+hipError_t launch_chi2_pvalue(const double* stat, double* pv, int64_t S, int dof, hipStream_t st);
 
 // seriesStats / removeInstantsWithNaNs / toInstants (sts_instants.hip)
 hipError_t launch_series_stats(const double* in, double* out, int64_t S, int64_t T, int64_t ld, hipStream_t st);

@@ -47,6 +47,34 @@ __device__ __forceinline__ double bsum(double v, double* red) {
     return v;
 }
 
+// The first `live` (uniform) of N sums at once: their butterflies interleave, so a wave waits for
+// one chain of shuffles, not `live` of them (red: N x 4 doubles when NT > 64)
+template <int NT, int N>
+__device__ __forceinline__ void bsum_many(double (&v)[N], int live, double* red) {
+#pragma unroll
+    for (int o = 32; o; o >>= 1)
+#pragma unroll
+        for (int c = 0; c < N; c++)
+            if (c < live) v[c] += __shfl_xor(v[c], o, 64);
+    if constexpr (NT > 64) {
+        __syncthreads();   // red[] free again
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int c = 0; c < N; c++)
+                if (c < live) red[c * 4 + (threadIdx.x >> 6)] = v[c];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < N; c++)
+            if (c < live) {
+                double t = red[c * 4];
+#pragma unroll
+                for (int i = 1; i < NT / 64; i++) t += red[c * 4 + i];
+                v[c] = t;
+            }
+    }
+}
+
 template <int NT>
 __device__ __forceinline__ double bscan(double v, double* red, double& total) {
     const int lane = threadIdx.x & 63;
@@ -482,7 +510,337 @@ __global__ void lb_kernel(const double* __restrict__ acf, int64_t S, int64_t T, 
     if (pv) pv[s] = 1.0 - gamma_p(0.5 * (double)K, 0.5 * q);
 }
 
+// ---- Breusch-Pagan (:311-319) and Breusch-Godfrey (:266-278): n R^2 of an OLS with intercept ----
+// The regressors are 1, the k factors (rows lo..lo+n of each factor row; lo = maxLag for BG, 0 for
+// BP) and, for BG, the lags e[t-1]..e[t-L] of the response e[L..T).  R^2 is formed as the
+// explained sum of squares over the centred total, a sum of non-negative terms:
+//   ESS = sum_c (q_c . y)^2 + |Lz^-1 Z'z_0|^2,     R^2 = ESS / (y . y)
+// with y the centred response, q_1..q_k an orthonormal basis of the centred factors
+// (factor_basis_kernel), z_j the lag-j window with its mean and its q components taken out, z_0
+// the response treated alike and Lz the Cholesky factor of the lags' Gram matrix Z'Z alone (as
+// adf_kernel).  No term is a difference of large numbers, so R^2 keeps its relative accuracy
+// where 1 - RSS / TSS and a pivot of the whole Gram matrix lose theirs.
+
+// A remainder of at most this share of the centred column counts as none: twice-applied
+// Gram-Schmidt leaves rounding noise of a few ulps of the column where exact arithmetic leaves 0
+// (a duplicated factor), and a factor collinear to 1e-6 leaves a million times the bound.
+constexpr double kBasisTol2 = 0x1p-80;   // (2^-40)^2, on squared norms
+
+// The orthonormal basis of one factor matrix: Q (k x n, row c at Q + c * n; global scratch or LDS),
+// from rows 0..n of the k factor rows at F; true when the factors are rank deficient.  Each thread
+// owns its rows i = tid, tid + NT, .. of every column, so the in-place sweeps need no ordering
+// between threads; only the dot products cross lanes.
+template <int NT>
+__device__ __forceinline__ bool build_basis(const double* __restrict__ F, int64_t ld_f, int k, int64_t n, double* Q,
+                                            double* red) {
+    const int tid = threadIdx.x;
+    const double dn = (double)n;
+    for (int j = 0; j < k; j++) {
+        const double* __restrict__ f = F + (int64_t)j * ld_f;
+        double* q = Q + (int64_t)j * n;
+        // centred column: sums on f - f[0] so that the level does not eat the spread's digits
+        const double f0 = f[0];
+        double acc = 0.0;
+        for (int64_t i = tid; i < n; i += NT) acc += f[i] - f0;
+        const double mu = bsum<NT>(acc, red) / dn;
+        acc = 0.0;
+        for (int64_t i = tid; i < n; i += NT) {
+            const double v = (f[i] - f0) - mu;
+            q[i] = v;
+            acc += v;
+        }
+        const double mu2 = bsum<NT>(acc, red) / dn;
+        acc = 0.0;
+        for (int64_t i = tid; i < n; i += NT) {
+            const double v = q[i] - mu2;
+            q[i] = v;
+            acc += v * v;
+        }
+        const double c2 = bsum<NT>(acc, red);
+        // modified Gram-Schmidt against the earlier columns, twice
+        for (int pass = 0; pass < 2; pass++)
+            for (int c = 0; c < j; c++) {
+                const double* qc = Q + (int64_t)c * n;
+                acc = 0.0;
+                for (int64_t i = tid; i < n; i += NT) acc += qc[i] * q[i];
+                const double d = bsum<NT>(acc, red);
+                for (int64_t i = tid; i < n; i += NT) q[i] -= d * qc[i];
+            }
+        acc = 0.0;
+        for (int64_t i = tid; i < n; i += NT) acc += q[i] * q[i];
+        const double w2 = bsum<NT>(acc, red);
+        if (w2 <= kBasisTol2 * c2) return true;   // uniform; NaN passes (NaN in, NaN out, status 0)
+        const double w = sqrt(w2);
+        for (int64_t i = tid; i < n; i += NT) q[i] /= w;
+    }
+    return false;
+}
+
+// One workgroup per factor matrix, into the scratch: a.basis, a.info (0 or STS_ERR_SINGULAR)
+template <int NT>
+__global__ __launch_bounds__(NT) void factor_basis_kernel(BgBpArgs a, int64_t s0) {
+    __shared__ double red[4];
+    const int64_t b = blockIdx.x;
+    const bool singular = build_basis<NT>(a.factors + (s0 + b) * a.fs + a.lo, a.ld_f, a.k, a.n,
+                                          a.basis + b * a.basis_stride, red);
+    if (threadIdx.x == 0) a.info[b] = singular ? STS_ERR_SINGULAR : 0;
+}
+
+// The basis of a stat kernel's series: OWN builds it from the series' own factors into LDS behind
+// the series (per-series factors that fit, one-wave form); otherwise it is in the scratch.  False
+// when the factors are rank deficient (the statistic is then NaN, the status STS_ERR_SINGULAR).
+template <int NT, bool OWN>
+__device__ __forceinline__ bool series_basis(const BgBpArgs& a, int64_t s, int64_t b, double* lds, double* red,
+                                             const double*& Q) {
+    bool singular;
+    if constexpr (OWN) {
+        singular = build_basis<NT>(a.factors + s * a.fs + a.lo, a.ld_f, a.k, a.n, lds, red);
+        Q = lds;
+    } else {
+        singular = a.info[b * a.info_stride] != 0;
+        Q = a.basis + b * a.basis_stride;
+    }
+    if (singular && threadIdx.x == 0) {
+        a.stat[s] = NAN;
+        if (a.err) a.err[s] = STS_ERR_SINGULAR;
+    }
+    return !singular;
+}
+
+// Breusch-Godfrey, one workgroup per series.  Window j (j = 0 the response, j = 1..L lag j) is rows
+// W(j, i) = e[L + i - j], i < n = T - L.
+template <int NT, bool LDS, bool OWN>
+__global__ __launch_bounds__(NT) void bg_kernel(BgBpArgs a, int64_t s0) {
+    extern __shared__ double dyn[];
+    __shared__ double red[8 * 4];
+    __shared__ double P[kMaxCols][kMaxFactors];   // P[j][c] = q_c . (centred window j)
+    __shared__ double mu[kMaxCols];
+    __shared__ double G[kMaxCols][kMaxCols + 1];
+    const int64_t b = blockIdx.x, s = s0 + b;
+    const double* __restrict__ g = a.in + s * a.ld;
+    const int64_t T = a.T, n = a.n;
+    const int tid = threadIdx.x, L = a.L, k = a.k;
+    const double dn = (double)n;
+    const double* Q;
+    if (!series_basis<NT, OWN>(a, s, b, dyn + T, red, Q)) return;   // uniform
+    if constexpr (LDS) {
+        for (int64_t t = tid; t < T; t += NT) dyn[t] = g[t];
+        __syncthreads();
+    }
+    auto X = [&](int64_t t) -> double {
+        if constexpr (LDS) return dyn[t];
+        else return g[t];
+    };
+    // window means, sums taken on x - x0
+    const double x0 = X(L);
+    for (int j = 0; j <= L; j++) {
+        double acc = 0.0;
+        for (int64_t i = tid; i < n; i += NT) acc += X(L + i - j) - x0;
+        acc = bsum<NT>(acc, red) / dn;
+        if (tid == 0) mu[j] = acc;
+    }
+    __syncthreads();
+    auto CEN = [&](int j, int64_t i) -> double { return (X(L + i - j) - x0) - mu[j]; };
+    // the centred total, and the factor components of every window
+    double tss = 0.0;
+    for (int64_t i = tid; i < n; i += NT) {
+        const double v = CEN(0, i);
+        tss += v * v;
+    }
+    tss = bsum<NT>(tss, red);
+    if (tss == 0.0) {   // a bit-constant response: the reference's 0 / 0
+        if (tid == 0) a.stat[s] = NAN;
+        return;
+    }
+    for (int j = 0; j <= L; j++) {
+        double acc[kMaxFactors];
+#pragma unroll
+        for (int c = 0; c < kMaxFactors; c++) acc[c] = 0.0;
+        for (int64_t i = tid; i < n; i += NT) {
+            const double v = CEN(j, i);
+#pragma unroll
+            for (int c = 0; c < kMaxFactors; c++)
+                if (c < k) acc[c] += Q[(int64_t)c * n + i] * v;
+        }
+        bsum_many<NT>(acc, k, red);
+        if (tid == 0) {
+#pragma unroll
+            for (int c = 0; c < kMaxFactors; c++)
+                if (c < k) P[j][c] = acc[c];
+        }
+    }
+    __syncthreads();
+    double ess = 0.0;
+    for (int c = 0; c < k; c++) ess += P[0][c] * P[0][c];
+    bool singular = false;
+    if (L > 0) {
+        // Gram matrix of the residualised lags (index j - 1) with the residualised response as
+        // row / column L, eight columns to a sweep
+        auto col_of = [&](int c) -> int { return c < L ? c + 1 : 0; };
+        for (int ca = 0; ca < L; ca++) {
+            const int ja = col_of(ca);
+            for (int cb0 = ca; cb0 <= L; cb0 += 8) {
+                double acc[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) acc[u] = 0.0;
+                for (int64_t i = tid; i < n; i += NT) {
+                    double qv[kMaxFactors];
+#pragma unroll
+                    for (int c = 0; c < kMaxFactors; c++) qv[c] = c < k ? Q[(int64_t)c * n + i] : 0.0;
+                    double za = CEN(ja, i);
+#pragma unroll
+                    for (int c = 0; c < kMaxFactors; c++)
+                        if (c < k) za -= P[ja][c] * qv[c];
+#pragma unroll
+                    for (int u = 0; u < 8; u++) {
+                        const int cb = cb0 + u;
+                        if (cb <= L) {
+                            const int jb = col_of(cb);
+                            double zb = CEN(jb, i);
+#pragma unroll
+                            for (int c = 0; c < kMaxFactors; c++)
+                                if (c < k) zb -= P[jb][c] * qv[c];
+                            acc[u] += za * zb;
+                        }
+                    }
+                }
+                bsum_many<NT>(acc, L + 1 - cb0, red);
+                if (tid == 0) {
+#pragma unroll
+                    for (int u = 0; u < 8; u++) {
+                        const int cb = cb0 + u;
+                        if (cb <= L) {
+                            G[ca][cb] = acc[u];
+                            G[cb][ca] = acc[u];
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        // Cholesky of the lag block, one thread per row; row L becomes Lz^-1 Z'z_0.  A zero or
+        // negative pivot is the reference's SingularMatrixException; NaN pivots pass.
+        for (int j = 0; j < L; j++) {
+            double d2 = G[j][j];
+            for (int c = 0; c < j; c++) d2 -= G[j][c] * G[j][c];
+            if (d2 <= 0.0) {
+                singular = true;
+                break;
+            }
+            const double d = sqrt(d2);
+            if (tid > j && tid <= L) {
+                double v = G[tid][j];
+                for (int c = 0; c < j; c++) v -= G[tid][c] * G[j][c];
+                G[tid][j] = v / d;
+            }
+            __syncthreads();
+        }
+        if (!singular)
+            for (int j = 0; j < L; j++) ess += G[L][j] * G[L][j];
+    }
+    if (tid == 0) {
+        if (singular) {
+            a.stat[s] = NAN;
+            if (a.err) a.err[s] = STS_ERR_SINGULAR;
+        } else {
+            a.stat[s] = dn * (ess / tss);
+        }
+    }
+}
+
+// Breusch-Pagan alone: no lags, so no Gram matrix and no LDS beyond the series.  With shared
+// factors this is the one-read kernel: the series comes from HBM once (into LDS in the one-wave
+// form), the k basis rows come from the caches, and k + 1 dot products and a sum of squares remain.
+template <int NT, bool LDS, bool OWN>
+__global__ __launch_bounds__(NT) void bp_kernel(BgBpArgs a, int64_t s0) {
+    extern __shared__ double dyn[];
+    __shared__ double red[(kMaxFactors + 1) * 4];
+    const int64_t b = blockIdx.x, s = s0 + b;
+    const double* __restrict__ g = a.in + s * a.ld;
+    const int64_t T = a.T;
+    const int tid = threadIdx.x, k = a.k;
+    const double dn = (double)T;
+    const double* Q;
+    if (!series_basis<NT, OWN>(a, s, b, dyn + T, red, Q)) return;   // uniform
+    // sweep 1: the mean of e^2, sums taken on e^2 - e[0]^2
+    const double e0 = g[0], x0 = e0 * e0;
+    double m = 0.0;
+    for (int64_t t = tid; t < T; t += NT) {
+        const double e = g[t], d = e * e - x0;
+        if constexpr (LDS) dyn[t] = d;
+        m += d;
+    }
+    m = bsum<NT>(m, red) / dn;
+    auto D = [&](int64_t t) -> double {
+        if constexpr (LDS) return dyn[t];   // each thread reads back its own steps
+        else {
+            const double e = g[t];
+            return e * e - x0;
+        }
+    };
+    // sweep 2: the centred total and the factor components
+    double acc[kMaxFactors + 1];
+#pragma unroll
+    for (int c = 0; c <= kMaxFactors; c++) acc[c] = 0.0;
+    for (int64_t t = tid; t < T; t += NT) {
+        const double v = D(t) - m;
+        acc[0] += v * v;
+#pragma unroll
+        for (int c = 0; c < kMaxFactors; c++)
+            if (c < k) acc[1 + c] += Q[(int64_t)c * T + t] * v;
+    }
+    bsum_many<NT>(acc, k + 1, red);
+    if (tid == 0) {
+        const double tss = acc[0];
+        double ess = 0.0;
+#pragma unroll
+        for (int c = 0; c < kMaxFactors; c++)
+            if (c < k) ess += acc[1 + c] * acc[1 + c];
+        a.stat[s] = tss == 0.0 ? NAN : dn * (ess / tss);   // a bit-constant response: the reference's 0 / 0
+    }
+}
+
+// 1 - chi2cdf(stat, dof), one lane per series (commons-math3 ChiSquaredDistribution, as lb_kernel)
+__global__ void chi2_pvalue_kernel(const double* __restrict__ stat, double* __restrict__ pv, int64_t S, int dof) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    pv[s] = 1.0 - gamma_p(0.5 * (double)dof, 0.5 * stat[s]);
+}
+
 }  // namespace
+
+// per-series factors of a one-wave series whose basis fits the LDS budget next to the series: the
+// stat kernel builds it there, and no scratch basis is needed
+constexpr size_t kOwnBasisLds = 48 << 10;
+bool own_basis(const BgBpArgs& a) {
+    return a.fs != 0 && a.T <= kStatOneWave && (size_t)(a.T + a.k * a.n) * sizeof(double) <= kOwnBasisLds;
+}
+
+hipError_t launch_factor_basis(const BgBpArgs& a, int64_t s0, int64_t nb, hipStream_t st) {
+    if (own_basis(a)) return hipSuccess;
+    hipLaunchKernelGGL(factor_basis_kernel<kLongThreads>, dim3((unsigned)nb), dim3(kLongThreads), 0, st, a, s0);
+    return hipGetLastError();
+}
+
+hipError_t launch_bgbp(const BgBpArgs& a, int64_t s0, int64_t ns, hipStream_t st) {
+    const dim3 grid((unsigned)ns);
+    const size_t series = (size_t)a.T * sizeof(double), own = (size_t)(a.T + a.k * a.n) * sizeof(double);
+    if (a.squares) {
+        if (own_basis(a)) hipLaunchKernelGGL((bp_kernel<64, true, true>), grid, dim3(64), own, st, a, s0);
+        else if (a.T <= kStatOneWave) hipLaunchKernelGGL((bp_kernel<64, true, false>), grid, dim3(64), series, st, a, s0);
+        else hipLaunchKernelGGL((bp_kernel<kLongThreads, false, false>), grid, dim3(kLongThreads), 0, st, a, s0);
+    } else {
+        if (own_basis(a)) hipLaunchKernelGGL((bg_kernel<64, true, true>), grid, dim3(64), own, st, a, s0);
+        else if (a.T <= kStatOneWave) hipLaunchKernelGGL((bg_kernel<64, true, false>), grid, dim3(64), series, st, a, s0);
+        else hipLaunchKernelGGL((bg_kernel<kLongThreads, false, false>), grid, dim3(kLongThreads), 0, st, a, s0);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_chi2_pvalue(const double* stat, double* pv, int64_t S, int dof, hipStream_t st) {
+    hipLaunchKernelGGL(chi2_pvalue_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, stat, pv, S, dof);
+    return hipGetLastError();
+}
 
 hipError_t launch_dw(const StatArgs& a, hipStream_t st) {
     if (a.T <= kStatOneWave) hipLaunchKernelGGL(dw_kernel<64>, dim3((unsigned)a.S), dim3(64), 0, st, a);

@@ -108,10 +108,16 @@ SIGNATURES = {
     "sts_kpss_test": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
     "sts_dw_test": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
     "sts_lb_test": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_vp]),
+    "sts_bp_test": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_int, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "sts_bg_test": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_int, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_vp,
+                             _c_vp]),
     "sts_adf_test_host": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     "sts_kpss_test_host": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp]),
     "sts_dw_test_host": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp]),
     "sts_lb_test_host": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp]),
+    "sts_bp_test_host": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_int, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp]),
+    "sts_bg_test_host": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_int, _c_i64, _c_i64, _c_int, _c_vp, _c_vp,
+                                  _c_vp]),
 }
 
 _lib = None

@@ -7,8 +7,8 @@ tensors take the device path on torch's current stream, numpy arrays the host-st
 (`_host`) path, exactly as UnivariateTimeSeries.autocorr does.  A series gives scalars, a panel
 gives (S,) arrays of the input's kind.
 
-bgtest and bptest are absent: they take a per-series factor matrix, which the C ABI has no
-shape for.
+The object's other two functions, bgtest and bptest, take a factor matrix next to the residuals:
+they are in sparkts.stats.factor_tests (t5 / t6) and exported from sparkts.stats like these four.
 """
 from __future__ import annotations
 

@@ -1,5 +1,6 @@
 """com.cloudera.sparkts.stats: batched statistical tests over series and panels."""
-from . import TimeSeriesStatisticalTests
+from . import TimeSeriesStatisticalTests, factor_tests
 from .TimeSeriesStatisticalTests import adftest, dwtest, kpsstest, lbtest
+from .factor_tests import bgtest, bptest
 
-__all__ = ["TimeSeriesStatisticalTests", "adftest", "dwtest", "kpsstest", "lbtest"]
+__all__ = ["TimeSeriesStatisticalTests", "factor_tests", "adftest", "bgtest", "bptest", "dwtest", "kpsstest", "lbtest"]

@@ -81,6 +81,17 @@ class TimeSeriesRDD:
         from .stats import TimeSeriesStatisticalTests as tst
         return tst.lbtest(self.data, maxLag)
 
+    def bgtest(self, factors, maxLag: int):
+        """rdd.mapValues(bgtest(_, factors, maxLag)): (statistics, p-values); factors (T, k) shared or
+        (S, T, k) per series."""
+        from .stats import factor_tests
+        return factor_tests.bgtest(self.data, factors, maxLag)
+
+    def bptest(self, factors):
+        """rdd.mapValues(bptest(_, factors)): (statistics, p-values)."""
+        from .stats import factor_tests
+        return factor_tests.bptest(self.data, factors)
+
     def fillAndAutocorr(self, method: str, numLags: int):
         """fill(method) followed by autocorr of every filled series, fused into one pass
         over HBM.  Returns (filled TimeSeriesRDD, acf (S, K))."""

@@ -1,17 +1,23 @@
 #!/usr/bin/env python3
-"""Time the batched statistical tests (sts_dw_test, sts_kpss_test, sts_adf_test, sts_lb_test) at
-the flagship panel shapes, next to three yardsticks measured in the SAME process, alternating
+"""Time the batched statistical tests (sts_dw_test, sts_kpss_test, sts_adf_test, sts_lb_test,
+sts_bp_test, sts_bg_test) at the flagship panel shapes, next to three yardsticks measured in the SAME process, alternating
 call by call with the case being measured:
 
   sts_series_stats   the one-read kernel on the same panel (the rate a one-sweep kernel can reach)
   sts_autocorr       at the Ljung-Box K (what sts_lb_test adds is the epilogue)
   torch              Durbin-Watson composed from torch ops on the device
+  sts_dw_test        for Breusch-Pagan (the other one-read residual test)
+  sts_adf_test       (5, ct) for Breusch-Godfrey at maxLag 5 (the other lag-Gram kernel)
+
+Breusch-Pagan and Breusch-Godfrey (maxLag 1 and 5) run with k = 3 factors, once shared by the panel
+and once per series.
 
 HIP events around every call, every shape warmed up first, --reps timed calls per case (>= 20).
 One JSON line per case: median / min ms, the yardstick's, their ratio, achieved bytes/s
 (8 S T over the median) and the library's sha256.
 
-    python tools/stattests_timing.py [--reps 20] [--out profiles/stattests_timing.jsonl]
+    python tools/stattests_timing.py [--reps 20] [--cases all|t1t4|bgbp] [--append]
+                                     [--out profiles/stattests_timing.jsonl]
 """
 import argparse
 import hashlib
@@ -31,6 +37,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--scale", type=float, default=1.0, help="scale S (a quick look on a busy machine)")
+    ap.add_argument("--cases", choices=["all", "t1t4", "bgbp"], default="all")
+    ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
     a = ap.parse_args()
     assert a.reps >= 20 or a.scale != 1.0, "at least 20 timed calls per case"
     import torch
@@ -40,7 +48,7 @@ def main():
     with open(_native.LIB_PATH, "rb") as f:
         lib_hash = hashlib.sha256(f.read()).hexdigest()[:16]
     sp = torch.cuda.current_stream().cuda_stream
-    out = open(a.out, "w") if a.out else None
+    out = open(a.out, "a" if a.append else "w") if a.out else None
 
     def timed_pair(fn, yard, reps):
         """Alternate fn / yard, one event pair per call -> (list of ms, list of ms)."""
@@ -97,6 +105,40 @@ def main():
             ("lb_20_vs_stats", lambda: lib.sts_lb_test(X, S, T, T, K, stat.data_ptr(), pv.data_ptr(), sp), series_stats,
              "sts_series_stats"),
         ]
+        if a.cases == "bgbp":
+            cases = []
+        if a.cases != "t1t4":
+            k = 3
+            fshared = torch.randn((k, T), dtype=torch.float64, device="cuda")
+            fper = torch.randn((S, k, T), dtype=torch.float64, device="cuda")
+            FS, FP = fshared.data_ptr(), fper.data_ptr()
+
+            def dw():
+                assert lib.sts_dw_test(X, S, T, T, stat.data_ptr(), sp) == 0
+
+            def adf_5_ct():
+                assert lib.sts_adf_test(X, S, T, T, 5, REG_CT, stat.data_ptr(), pv.data_ptr(), err.data_ptr(), sp) == 0
+
+            def bp(f, fs):
+                return lambda: lib.sts_bp_test(X, S, T, T, f, k, T, fs, stat.data_ptr(), pv.data_ptr(), err.data_ptr(), sp)
+
+            def bg(f, fs, lag):
+                return lambda: lib.sts_bg_test(X, S, T, T, f, k, T, fs, lag, stat.data_ptr(), pv.data_ptr(),
+                                               err.data_ptr(), sp)
+
+            cases += [
+                ("bp_3_shared", bp(FS, 0), series_stats, "sts_series_stats"),
+                ("bp_3_shared_vs_dw", bp(FS, 0), dw, "sts_dw_test"),
+                ("bp_3_per_series", bp(FP, k * T), series_stats, "sts_series_stats"),
+                ("bp_3_per_series_vs_dw", bp(FP, k * T), dw, "sts_dw_test"),
+                ("bg_1_3_shared", bg(FS, 0, 1), series_stats, "sts_series_stats"),
+                ("bg_1_3_per_series", bg(FP, k * T, 1), series_stats, "sts_series_stats"),
+                ("bg_5_3_shared", bg(FS, 0, 5), series_stats, "sts_series_stats"),
+                ("bg_5_3_shared_vs_dw", bg(FS, 0, 5), dw, "sts_dw_test"),
+                ("bg_5_3_shared_vs_adf", bg(FS, 0, 5), adf_5_ct, "sts_adf_test(5, ct)"),
+                ("bg_5_3_per_series", bg(FP, k * T, 5), series_stats, "sts_series_stats"),
+                ("bg_5_3_per_series_vs_adf", bg(FP, k * T, 5), adf_5_ct, "sts_adf_test(5, ct)"),
+            ]
         for name, fn, yard, yname in cases:
             ms, yms = timed_pair(fn, yard, a.reps)
             rec = {"case": name, "S": S, "T": T, "reps": a.reps, "ms_median": med(ms), "ms_min": min(ms),
@@ -108,7 +150,9 @@ def main():
             if out:
                 out.write(line + "\n")
                 out.flush()
-        del x, stat, pv, st4, acf, err
+        del x, stat, pv, st4, acf, err, cases
+        if a.cases != "t1t4":
+            del fshared, fper
         torch.cuda.empty_cache()
 
 
