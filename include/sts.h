@@ -45,6 +45,25 @@
  * through HBM on the calling thread's stream and return when the results
  * are back on the host (the JNI path).
  *
+ * Stream contract (every entry point whose last parameter is `stream`; pinned by
+ * tests/test_stream_order_gpu.py, one row per entry point, on non-blocking streams):
+ *   - every launch, memset, copy and scratch allocation / release of a call is queued on
+ *     `stream` and nowhere else: the call reads its inputs after the work queued on `stream`
+ *     before it and its outputs are complete for the work queued after it, whatever other
+ *     streams are doing;
+ *   - a call returns without waiting for the device, except: a call that takes
+ *     err_per_series and is given NULL (it waits and reports the first failing series),
+ *     sts_autocorr (it is sts_fill_autocorr with NULL), sts_ar_rule_count (its result is a
+ *     host value), sts_fill_autocorr with T == 0 and K > 0, and sts_stream_synchronize;
+ *   - two calls on two streams share nothing: scratch is allocated per call, stream-ordered.
+ * A caller on the legacy null stream that passes NULL (the Python mirror on torch's default
+ * stream does: that stream's handle is 0) has its work on hipStreamPerThread while its
+ * producers and consumers sit on the legacy null stream, and nothing in this library orders
+ * the two.  Observed on an MI355X, not guaranteed here: behind a producer delayed by 20 ms on
+ * the legacy stream the mirror's pipelines return the bits of the undelayed call, i.e. the
+ * runtime ordered the two streams in both directions
+ * (test_stream_order_gpu.py::test_mirror[*-default_stream] pins it).
+ *
  * Errors: every function returns an sts_status; sts_last_error() gives a
  * thread-local message.  Per-series data errors (fillNearest on an all-NaN
  * series, singular AR designs) are written to an optional device int32

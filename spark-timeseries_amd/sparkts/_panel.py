@@ -4,6 +4,16 @@ Device path: torch CUDA(HIP) float64 tensors, (T,) for one series or (S, T) for 
 panel with unit stride along time; the call runs on torch's current stream.
 Host path: numpy float64 arrays; the `_host` C entry points stage them through HBM
 (the JNI path).  torch is plumbing only (device memory + streams).
+
+Streams: `Panel.stream` (and `io._stream`) hand the library the handle of torch's current stream.
+Inside `with torch.cuda.stream(side)` that is `side` itself, and every launch of the call is
+queued there (include/sts.h, "Stream contract").  On torch's default stream the handle is 0,
+which the library takes as NULL = hipStreamPerThread, while torch's own producers and consumers
+run on the legacy null stream: nothing in this package orders the two.  The mirror relies on the
+HIP runtime doing so.  That is an observed result, not a guarantee of this package:
+tests/test_stream_order_gpu.py::test_mirror[*-default_stream] (delayed producer, mirror call,
+`.cpu()` reads, all on the default stream) gives the undelayed call's bits on an MI355X and pins
+it; io.toWire waits for the stream itself before its library call and shows nothing either way.
 """
 from __future__ import annotations
 
