@@ -208,7 +208,9 @@ __device__ __forceinline__ bool acf_suspect(double r, double sum1, double sq1, d
     const double d1 = 0x1p-55 * N * (__builtin_fabs(c) + __builtin_sqrt(sq1 / N));
     const double d2 = 0x1p-55 * N * (__builtin_fabs(c) + __builtin_sqrt(sq2 / N));
     const double e_ref = N * d1 * d2 / __builtin_sqrt(v1 * v2) + ar * 0.5 * (N * d1 * d1 / v1 + N * d2 * d2 / v2);
-    return e_ours + e_ref > __builtin_fmax(1e-11 * ar, eps * rn);
+    // negated <=: a NaN or infinite estimate (overflow / underflow of the moments' products at
+    // extreme data scales) is suspect, never trusted
+    return !(e_ours + e_ref <= __builtin_fmax(1e-11 * ar, eps * rn));
 }
 
 // The same test at a fraction of its VALU (round 6, the issue-bound short kernel): hardware
@@ -232,7 +234,7 @@ __device__ __forceinline__ bool acf_suspect_fast(double r, double sum1, double s
     const double d1 = 0x1p-55 * N * (__builtin_fabs(c) + m1 * __builtin_amdgcn_rsq(m1));
     const double d2 = 0x1p-55 * N * (__builtin_fabs(c) + m2 * __builtin_amdgcn_rsq(m2));
     const double e_ref = N * d1 * d2 * __builtin_amdgcn_rsq(v1 * v2) + ar * 0.5 * (N * d1 * d1 * iv1 + N * d2 * d2 * iv2);
-    return (e_ours + e_ref) * 1.001 > __builtin_fmax(1e-11 * ar, eps * rn);
+    return !((e_ours + e_ref) * 1.001 <= __builtin_fmax(1e-11 * ar, eps * rn));   // fail safe on NaN, as above
 }
 
 // The reference's autocorr of lag i (1 <= i < T) over F (S/UnivariateTimeSeries.scala:71-89,

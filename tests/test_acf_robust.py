@@ -204,7 +204,7 @@ def acf_suspect(r, s1, q1, s2, q2, v1, v2, N, c):
     d1 = 2.0 ** -55 * N * (abs(c) + np.sqrt(q1 / N))
     d2 = 2.0 ** -55 * N * (abs(c) + np.sqrt(q2 / N))
     e_ref = N * d1 * d2 / np.sqrt(v1 * v2) + ar * 0.5 * (N * d1 * d1 / v1 + N * d2 * d2 / v2)
-    return e_ours + e_ref > max(1e-11 * ar, EPS * rn)
+    return not (e_ours + e_ref <= max(1e-11 * ar, EPS * rn))   # a NaN estimate is suspect
 
 
 def suspect_lags(x, K, c=None):
