@@ -381,11 +381,12 @@ int series_status(const int32_t* h, int64_t S, const char* what) {
 
 int set_error(int status, const char* msg) { return fail(status, "%s", msg); }
 
-int validate_call(int (*fn)(void*), void* ctx) {
+int validate_call(int (*fn)(void*), void* ctx, bool* has_work) {
     g_validate_only = true;
     const int r = fn(ctx);
     g_validate_only = false;
-    return r == kValidated ? STS_OK : r;
+    *has_work = r == kValidated;   // stopped in ensure_device(); STS_OK: returned before it
+    return *has_work ? STS_OK : r;
 }
 
 }  // namespace sts

@@ -12,6 +12,14 @@
 // by DMA directly, with no bounce copy; pageable memory goes through the slot's pinned
 // buffer (one CPU copy, the same one hipMemcpy would make internally, but overlapped).
 //
+// One description per call.  A `_host` wrapper lists its per-series arrays (Arg) once and writes
+// its device call once, against a Call; staged() runs that call first in validate-only mode
+// (sts::validate) on the caller's host pointers, S and ld -- so every argument check, its order
+// and its message are the device entry point's own, and a call the entry point answers before any
+// device action (an empty panel, lag 0) stages nothing -- and then once per chunk on the chunk's
+// device regions.  An output whose host pointer is an input's (an in-place call) shares that
+// input's device region; an argument passed as NULL is NULL on the device too.
+//
 // Every device entry point runs on the slot's stream; per-series statuses always go to a
 // device array and come back with the chunk, so a NULL err_per_series keeps the reference's
 // exception semantics (the first failing series becomes the return status after all
@@ -51,9 +59,10 @@ constexpr int kSlots = STS_STAGE_SLOTS;
 constexpr size_t kChunkBytes = size_t(STS_STAGE_MB) << 20;   // device bytes (in + out) per chunk
 constexpr size_t kAlign = 256;
 constexpr int kDefaultSets = 4;                                // slot sets per device (sts_staging_set_limit)
+constexpr size_t kMaxArgs = 16;                                // per-series arrays of one call (staged() checks)
 // what a slot keeps between calls: one chunk plus the per-argument alignment; a call whose single
 // series is larger than a chunk grows its slots for that call only (Borrow trims them again)
-constexpr size_t kSlotKeep = kChunkBytes + 16 * kAlign;
+constexpr size_t kSlotKeep = kChunkBytes + kMaxArgs * kAlign;
 
 size_t align_up(size_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
 
@@ -177,11 +186,14 @@ bool is_pinned(const void* p) {
 // bytes per series); on the host, series s starts at s * hstride.
 struct Arg {
     const void* src = nullptr;   // host input (copied in), or nullptr
-    void* dst = nullptr;         // host output (copied out), or nullptr; == src for in place
+    void* dst = nullptr;         // host output (copied out), or nullptr
     size_t row = 0;              // device bytes per series
     size_t hstride = 0;          // host bytes between series
+    bool panel = false;          // row / hstride are the call's T / ld doubles: staged() sets them once validated
+    int shares = -1;             // an output on an input's host memory (an in-place call): that input's index
     bool pinned_src = false, pinned_dst = false;
     size_t dev_off = 0, pin_off = 0;   // per-slot layout (set per chunk size)
+    void* host() const { return src ? const_cast<void*>(src) : dst; }
 };
 
 Arg in_arg(const void* p, size_t row, size_t hstride) {
@@ -198,17 +210,39 @@ Arg out_arg(void* p, size_t row, size_t hstride) {
     a.hstride = hstride;
     return a;
 }
-Arg inout_arg(void* p, size_t row, size_t hstride) {
-    Arg a;
-    a.src = p;
-    a.dst = p;
-    a.row = row;
-    a.hstride = hstride;
+// a panel of the call: T doubles per series, ld apart on the host
+Arg in_panel(const double* p) {
+    Arg a = in_arg(p, 0, 0);
+    a.panel = true;
     return a;
 }
+Arg out_panel(double* p) {
+    Arg a = out_arg(p, 0, 0);
+    a.panel = true;
+    return a;
+}
+// n doubles per series, packed
+Arg in_vec(const double* p, int64_t n = 1) { return in_arg(p, (size_t)n * sizeof(double), (size_t)n * sizeof(double)); }
+Arg out_vec(double* p, int64_t n = 1) { return out_arg(p, (size_t)n * sizeof(double), (size_t)n * sizeof(double)); }
 
-// kernel(device pointers per arg (chunk-local, row-contiguous), first series, series, stream)
-using Kernel = std::function<int(void* const* dev, int64_t s0, int64_t ns, hipStream_t st)>;
+// What a wrapper's one device call is handed.  For validation: the caller's host pointers, S and
+// ld, and a null stream (the device entry point stops before it dereferences anything).  For a
+// chunk: the chunk's device regions (row-contiguous), its series count and its row length T as
+// ld, on the slot's stream.  An argument the caller passed as NULL is NULL in both.
+struct Call {
+    const std::vector<Arg>& args;
+    char* dev;
+    int64_t n, ld;
+    hipStream_t st;
+    void* at(size_t k) const {
+        void* h = args[k].host();
+        return st && h ? dev + args[k].dev_off : h;
+    }
+    const double* in(size_t k) const { return static_cast<const double*>(at(k)); }
+    double* out(size_t k) const { return static_cast<double*>(at(k)); }
+    int32_t* err(size_t k) const { return static_cast<int32_t*>(at(k)); }
+};
+using Kernel = std::function<int(const Call&)>;
 
 void copy_rows(void* dst, size_t dstride, const void* src, size_t sstride, size_t row, int64_t n) {
     if (dstride == row && sstride == row) {
@@ -241,21 +275,21 @@ int reap(Slot& sl, std::vector<Arg>& args) {
     return STS_OK;
 }
 
-// Run `kern` over S series in chunks through a borrowed slot set.
-int staged(int64_t S, std::vector<Arg> args, const Kernel& kern) {
+// Run `kern` -- the wrapper's one device call -- over S series of T steps (ld apart on the host)
+// in chunks through a borrowed slot set.
+int staged(int64_t S, int64_t T, int64_t ld, std::vector<Arg> args, const Kernel& kern) {
     const auto t_start = std::chrono::steady_clock::now();
     Stats& g = g_stats;
     g = Stats();
     int r;
-    // the device entry point's own argument checks first, on the caller's shapes and host
-    // pointers (never dereferenced in validate-only mode): no staging on bad input
-    {
-        void* hp[16];
-        for (size_t k = 0; k < args.size() && k < 16; k++)
-            hp[k] = const_cast<void*>(args[k].src ? args[k].src : static_cast<const void*>(args[k].dst));
-        if ((r = sts::validate([&] { return kern(hp, 0, S, nullptr); }))) return r;
-    }
-    if (S <= 0) return STS_OK;
+    if (args.size() > kMaxArgs) return sts::set_error(STS_ERR_BAD_ARG, "staging: too many per-series arguments");
+    // the device entry point's own argument checks first, on the caller's shapes, ld and host
+    // pointers (never dereferenced in validate-only mode): no staging on bad input, and none
+    // where the entry point returns before its first device action (an empty panel, lag 0)
+    bool work = false;
+    if ((r = sts::validate([&] { return kern(Call{args, nullptr, S, ld, nullptr}); }, &work))) return r;
+    // S = 0 on its own: sts_fill and sts_fill_autocorr reach the device with no series to launch
+    if (!work || S <= 0) return STS_OK;
     Borrow bw;
     {
         hipError_t e = hipGetDevice(&bw.dev);
@@ -264,9 +298,19 @@ int staged(int64_t S, std::vector<Arg> args, const Kernel& kern) {
     }
     Slot* slots = bw.set->slot;
     size_t per_series = 0;
-    for (Arg& x : args) {
+    for (size_t k = 0; k < args.size(); k++) {
+        Arg& x = args[k];
+        if (x.panel) x.row = (size_t)T * sizeof(double), x.hstride = (size_t)ld * sizeof(double);
+        // in place: an output on an earlier input's host rows lives in that input's device (and
+        // bounce) region and is copied out from there
+        for (size_t j = 0; j < k && x.dst && x.shares < 0; j++)
+            if (args[j].src == x.dst && args[j].row == x.row && args[j].hstride == x.hstride) x.shares = (int)j;
+        if (x.shares >= 0) {
+            x.pinned_dst = args[x.shares].pinned_src;
+            continue;
+        }
         x.pinned_src = is_pinned(x.src);
-        x.pinned_dst = (x.dst == x.src) ? x.pinned_src : is_pinned(x.dst);
+        x.pinned_dst = is_pinned(x.dst);
         per_series += x.row;
     }
     int64_t ns = per_series ? (int64_t)(kChunkBytes / per_series) : S;
@@ -274,6 +318,11 @@ int staged(int64_t S, std::vector<Arg> args, const Kernel& kern) {
     // per-slot layout: one device region per arg; one pinned region per pageable in / out
     size_t dev_bytes = 0, pin_bytes = 0;
     for (Arg& x : args) {
+        if (x.shares >= 0) {
+            x.dev_off = args[x.shares].dev_off;
+            x.pin_off = args[x.shares].pin_off;
+            continue;
+        }
         x.dev_off = dev_bytes;
         dev_bytes += align_up(x.row * (size_t)ns);
         x.pin_off = pin_bytes;
@@ -326,9 +375,7 @@ int staged(int64_t S, std::vector<Arg> args, const Kernel& kern) {
             if (x.pinned_src) g.direct += (double)n;
         }
         if ((e = hipEventRecord(sl.ev[1], sl.st)) != hipSuccess) return hip_status(e, "staging: event");
-        void* ptrs[16];
-        for (size_t k = 0; k < args.size() && k < 16; k++) ptrs[k] = dev + args[k].dev_off;
-        status = kern(ptrs, sl.s0, sl.ns, sl.st);
+        status = kern(Call{args, dev, sl.ns, T, sl.st});
         if ((e = hipEventRecord(sl.ev[2], sl.st)) != hipSuccess) return hip_status(e, "staging: event");
         if (status == STS_OK) {
             for (Arg& x : args) {
@@ -357,8 +404,6 @@ int staged(int64_t S, std::vector<Arg> args, const Kernel& kern) {
     return status;
 }
 
-size_t panel_stride(int64_t ld) { return (size_t)(ld > 0 ? ld : 0) * sizeof(double); }
-
 // Per-series statuses: the caller's host array, or an internal one whose first failure
 // becomes the return status (the reference's exception) once every chunk is back.
 struct ErrOut {
@@ -375,6 +420,7 @@ struct ErrOut {
         return sts::series_status(h, S, what);
     }
 };
+Arg status(ErrOut& eo) { return out_arg(eo.h, sizeof(int32_t), sizeof(int32_t)); }
 
 }  // namespace
 
@@ -426,305 +472,179 @@ int sts_staging_stats(double* out8) {
     return STS_OK;
 }
 
+// ---- the _host entry points.  Each lists its per-series arrays once and states its device call
+// once; staged() runs that call for validation (the caller's pointers, S and ld) and per chunk.
+// Every argument error, and every "nothing to do", is therefore the device entry point's own:
+// a check written here is one no device entry point can make, and says why it stays. ----
+
 int sts_fill_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int method, int32_t* err) {
-    const size_t row = (size_t)(T > 0 ? T : 0) * sizeof(double);
-    if (S > 0 && T > 0 && (!in || !out)) return sts::set_error(STS_ERR_BAD_ARG, "fill: null panel pointer");
-    if (in == out && S * T > 0) return sts::set_error(STS_ERR_BAD_ARG, "fill: out must not alias in (fillts returns a new vector)");
-    // validate through the device entry point's own checks first (no staging on bad input)
-    if (method < STS_FILL_LINEAR || method > STS_FILL_SPLINE)
-        return sts_fill(nullptr, nullptr, 0, 0, 0, 0, method, nullptr, nullptr);
-    if (ld < T) return sts_fill(in, out, S, T, ld, ld, method, nullptr, nullptr);
     ErrOut eo(err, S);
-    const int st = staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(out, row, panel_stride(ld)),
-                              out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
-                          [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                              return sts_fill(static_cast<const double*>(d[0]), static_cast<double*>(d[1]), n, T, T, T,
-                                              method, static_cast<int32_t*>(d[2]), s);
-                          });
+    const int st = staged(S, T, ld, {in_panel(in), out_panel(out), status(eo)}, [&](const Call& c) {
+        return sts_fill(c.in(0), c.out(1), c.n, T, c.ld, c.ld, method, c.err(2), c.st);
+    });
     return eo.finish(st, S, "fill");
 }
 
 int sts_autocorr_host(const double* in, int64_t S, int64_t T, int64_t ld, int K, double* acf) {
-    if (K < 0 || ld < T || (S > 0 && T > 0 && !in) || (S > 0 && K > 0 && !acf))
-        return sts_autocorr(in, S, T, ld, K, acf, nullptr);   // the device entry point's error
-    const size_t row = (size_t)(T > 0 ? T : 0) * sizeof(double), krow = (size_t)K * sizeof(double);
     // a device err array per chunk (it stays all zero: raw autocorr has no failing series), so
     // the device entry point never synchronises inside the pipeline
     ErrOut eo(nullptr, S);
-    const int st = staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(acf, krow, krow),
-                              out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
-                          [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                              return sts_fill_autocorr(static_cast<const double*>(d[0]), nullptr, n, T, T, T,
-                                                       STS_FILL_NONE, K, static_cast<double*>(d[1]),
-                                                       static_cast<int32_t*>(d[2]), s);
-                          });
+    const int st = staged(S, T, ld, {in_panel(in), out_vec(acf, K), status(eo)}, [&](const Call& c) {
+        return sts_fill_autocorr(c.in(0), nullptr, c.n, T, c.ld, c.ld, STS_FILL_NONE, K, c.out(1), c.err(2), c.st);
+    });
     return eo.finish(st, S, "autocorr");
 }
 
 int sts_fill_autocorr_host(const double* in, double* filled, int64_t S, int64_t T, int64_t ld, int method, int K,
                            double* acf, int32_t* err) {
-    if (method == STS_FILL_NONE) {
-        if (filled) return sts::set_error(STS_ERR_BAD_ARG, "fill_autocorr: filled must be NULL for STS_FILL_NONE");
-        return sts_autocorr_host(in, S, T, ld, K, acf);
-    }
-    if (method < STS_FILL_LINEAR || method > STS_FILL_SPLINE || K < 0 || ld < T ||
-        (S * T > 0 && (!in || !filled || in == filled)) || (S > 0 && K > 0 && !acf))
-        return sts_fill_autocorr(in, filled, S, T, ld, ld, method, K, acf, nullptr, nullptr);
-    const size_t row = (size_t)(T > 0 ? T : 0) * sizeof(double), krow = (size_t)K * sizeof(double);
+    // picks the code path: raw autocorr has no filled panel to stage and leaves the caller's err alone
+    if (method == STS_FILL_NONE && !filled) return sts_autocorr_host(in, S, T, ld, K, acf);
     ErrOut eo(err, S);
-    const int st = staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(filled, row, panel_stride(ld)),
-                              out_arg(acf, krow, krow), out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
-                          [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                              return sts_fill_autocorr(static_cast<const double*>(d[0]), static_cast<double*>(d[1]), n,
-                                                       T, T, T, method, K, static_cast<double*>(d[2]),
-                                                       static_cast<int32_t*>(d[3]), s);
-                          });
+    const int st = staged(S, T, ld, {in_panel(in), out_panel(filled), out_vec(acf, K), status(eo)}, [&](const Call& c) {
+        return sts_fill_autocorr(c.in(0), c.out(1), c.n, T, c.ld, c.ld, method, K, c.out(2), c.err(3), c.st);
+    });
     return eo.finish(st, S, "fill_autocorr");
 }
 
+// in == out is the reference's in-place recurrence (dest eq ts), per series; out of place
+// dest(i) = ts(i) for i < start (:363-369), so dest is fully written; lag 0 leaves dest untouched
 int sts_diff_at_lag_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int lag, int start) {
-    if (!(start >= lag) || lag <= 0 || ld < T || S * T == 0 || !in || !out)   // require(), lag 0: dest untouched
-        return sts_diff_at_lag(in, out, S, T, ld, ld, lag, start, nullptr);
-    const size_t row = (size_t)T * sizeof(double);
-    if (in == out)   // dest eq ts: the reference's in-place recurrence, per series
-        return staged(S, {inout_arg(out, row, panel_stride(ld))}, [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-            return sts_diff_at_lag(static_cast<double*>(d[0]), static_cast<double*>(d[0]), n, T, T, T, lag, start, s);
-        });
-    // out-of-place: dest(i) = ts(i) for i < start (:363-369), so dest is fully written
-    return staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(out, row, panel_stride(ld))},
-                  [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                      return sts_diff_at_lag(static_cast<const double*>(d[0]), static_cast<double*>(d[1]), n, T, T, T,
-                                             lag, start, s);
-                  });
+    return staged(S, T, ld, {in_panel(in), out_panel(out)}, [&](const Call& c) {
+        return sts_diff_at_lag(c.in(0), c.out(1), c.n, T, c.ld, c.ld, lag, start, c.st);
+    });
 }
 
 int sts_lag_matrix_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int max_lag, int inc) {
-    if (max_lag < 0 || max_lag > T || ld < T || (S * T > 0 && !in))
-        return sts_lag_matrix(in, out, S, T, ld, max_lag, inc, nullptr);
-    const int64_t rows = T - max_lag, cols = max_lag + (inc ? 1 : 0);
-    const size_t orow = (size_t)(rows * cols) * sizeof(double), row = (size_t)T * sizeof(double);
-    if (orow == 0 || S == 0) return STS_OK;
-    if (!out) return sts_lag_matrix(in, nullptr, S, T, ld, max_lag, inc, nullptr);
-    return staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(out, orow, orow)},
-                  [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                      return sts_lag_matrix(static_cast<const double*>(d[0]), static_cast<double*>(d[1]), n, T, T,
-                                            max_lag, inc, s);
-                  });
+    // a check of this wrapper's own, for the size alone: the matrix is sized only for a shape
+    // sts_lag_matrix accepts (T in the reference's Int range, 0 <= maxLag <= T), so the product cannot
+    // overflow; sts_lag_matrix rejects the rest with its own message
+    const bool sized = max_lag >= 0 && max_lag <= T && T <= 0x7fffffffLL;
+    const int64_t n = sized ? (T - max_lag) * ((int64_t)max_lag + (inc ? 1 : 0)) : 0;
+    return staged(S, T, ld, {in_panel(in), out_vec(out, n)}, [&](const Call& c) {
+        return sts_lag_matrix(c.in(0), c.out(1), c.n, T, c.ld, max_lag, inc, c.st);
+    });
 }
 
-static int ewma_host(bool add, const double* in, double* out, int64_t S, int64_t T, int64_t ld, const double* sm) {
-    auto dev_call = [&](const double* i, double* o, int64_t n, const double* m, hipStream_t s) {
-        return add ? sts_ewma_add(i, o, n, T, T, T, m, s) : sts_ewma_remove(i, o, n, T, T, T, m, s);
-    };
-    if (!out || ld < T || (S > 0 && !sm) || (S * T > 0 && !in))
-        return add ? sts_ewma_add(in, out, S, T, ld, ld, sm, nullptr) : sts_ewma_remove(in, out, S, T, ld, ld, sm, nullptr);
-    if (S * T == 0) return STS_OK;
-    const size_t row = (size_t)T * sizeof(double);
-    if (in == out)   // add: safe; remove: the reference's read-after-overwrite, per series
-        return staged(S, {inout_arg(out, row, panel_stride(ld)), in_arg(sm, sizeof(double), sizeof(double))},
-                      [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                          return dev_call(static_cast<double*>(d[0]), static_cast<double*>(d[0]), n,
-                                          static_cast<const double*>(d[1]), s);
-                      });
-    return staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(out, row, panel_stride(ld)),
-                      in_arg(sm, sizeof(double), sizeof(double))},
-                  [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                      return dev_call(static_cast<const double*>(d[0]), static_cast<double*>(d[1]), n,
-                                      static_cast<const double*>(d[2]), s);
-                  });
+// in == out: add is safe; remove is the reference's read-after-overwrite, per series
+static int ewma_host(decltype(&sts_ewma_add) fn, const double* in, double* out, int64_t S, int64_t T, int64_t ld,
+                     const double* sm) {
+    return staged(S, T, ld, {in_panel(in), out_panel(out), in_vec(sm)}, [&](const Call& c) {
+        return fn(c.in(0), c.out(1), c.n, T, c.ld, c.ld, c.in(2), c.st);
+    });
 }
 
 int sts_ewma_add_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, const double* sm) {
-    return ewma_host(true, in, out, S, T, ld, sm);
+    return ewma_host(sts_ewma_add, in, out, S, T, ld, sm);
 }
 
 int sts_ewma_remove_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, const double* sm) {
-    return ewma_host(false, in, out, S, T, ld, sm);
+    return ewma_host(sts_ewma_remove, in, out, S, T, ld, sm);
 }
 
 int sts_fill_diff_ewma_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int method, int lag,
                             const double* smoothing, int32_t* err) {
-    if (method < STS_FILL_NONE || method > STS_FILL_SPLINE || lag < 0 || ld < T ||
-        (S > 0 && !smoothing) || (S * T > 0 && (!in || !out || in == out)))
-        return sts_fill_diff_ewma(in, out, S, T, ld, ld, method, lag, smoothing, nullptr, nullptr);
-    if (S * T == 0) return STS_OK;
-    const size_t row = (size_t)T * sizeof(double);
     ErrOut eo(err, S);
-    const int st = staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(out, row, panel_stride(ld)),
-                              in_arg(smoothing, sizeof(double), sizeof(double)),
-                              out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
-                          [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                              return sts_fill_diff_ewma(static_cast<const double*>(d[0]), static_cast<double*>(d[1]), n,
-                                                        T, T, T, method, lag, static_cast<const double*>(d[2]),
-                                                        static_cast<int32_t*>(d[3]), s);
-                          });
+    const int st = staged(S, T, ld, {in_panel(in), out_panel(out), in_vec(smoothing), status(eo)}, [&](const Call& c) {
+        return sts_fill_diff_ewma(c.in(0), c.out(1), c.n, T, c.ld, c.ld, method, lag, c.in(2), c.err(3), c.st);
+    });
     return eo.finish(st, S, "fill_diff_ewma");
 }
 
 int sts_ewma_fit_host(const double* in, int64_t S, int64_t T, int64_t ld, double* smoothing, int32_t* err) {
-    if (ld < T || (S > 0 && (T < 1 || !smoothing || !in))) return sts_ewma_fit(in, S, T, ld, smoothing, nullptr, nullptr);
-    const size_t row = (size_t)T * sizeof(double);
     ErrOut eo(err, S);
-    const int st = staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(smoothing, sizeof(double), sizeof(double)),
-                              out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
-                          [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                              return sts_ewma_fit(static_cast<const double*>(d[0]), n, T, T, static_cast<double*>(d[1]),
-                                                  static_cast<int32_t*>(d[2]), s);
-                          });
+    const int st = staged(S, T, ld, {in_panel(in), out_vec(smoothing), status(eo)}, [&](const Call& c) {
+        return sts_ewma_fit(c.in(0), c.n, T, c.ld, c.out(1), c.err(2), c.st);
+    });
     return eo.finish(st, S, "EWMA.fitModel");
 }
 
 int sts_ar_fit_host(const double* in, int64_t S, int64_t T, int64_t ld, int p, int no_intercept, double* c,
                     double* coef, int32_t* err) {
-    if (ld < T || p < 1 || p > 31 || T - p < (int64_t)p + 1 || (S > 0 && (!c || !coef || !in)))
-        return sts_ar_fit(in, S, T, ld, p, no_intercept, c, coef, nullptr, nullptr);
-    const size_t row = (size_t)T * sizeof(double), prow = (size_t)p * sizeof(double);
     ErrOut eo(err, S);
-    const int st = staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(c, sizeof(double), sizeof(double)),
-                              out_arg(coef, prow, prow), out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
-                          [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                              return sts_ar_fit(static_cast<const double*>(d[0]), n, T, T, p, no_intercept,
-                                                static_cast<double*>(d[1]), static_cast<double*>(d[2]),
-                                                static_cast<int32_t*>(d[3]), s);
-                          });
+    const int st = staged(S, T, ld, {in_panel(in), out_vec(c), out_vec(coef, p), status(eo)}, [&](const Call& k) {
+        return sts_ar_fit(k.in(0), k.n, T, k.ld, p, no_intercept, k.out(1), k.out(2), k.err(3), k.st);
+    });
     return eo.finish(st, S, "ar_fit");
 }
 
 int sts_ar_fit_remove_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int p, int no_intercept,
                            double* c, double* coef, int32_t* err) {
-    if (!out || in == out || ld < T || p < 1 || p > 31 || T - p < (int64_t)p + 1 || (S > 0 && (!c || !coef || !in)))
-        return sts_ar_fit_remove(in, out, S, T, ld, ld, p, no_intercept, c, coef, nullptr, nullptr);
-    const size_t row = (size_t)T * sizeof(double), prow = (size_t)p * sizeof(double);
     ErrOut eo(err, S);
-    const int st = staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(out, row, panel_stride(ld)),
-                              out_arg(c, sizeof(double), sizeof(double)), out_arg(coef, prow, prow),
-                              out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
-                          [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                              return sts_ar_fit_remove(static_cast<const double*>(d[0]), static_cast<double*>(d[1]), n,
-                                                       T, T, T, p, no_intercept, static_cast<double*>(d[2]),
-                                                       static_cast<double*>(d[3]), static_cast<int32_t*>(d[4]), s);
+    const int st = staged(S, T, ld, {in_panel(in), out_panel(out), out_vec(c), out_vec(coef, p), status(eo)},
+                          [&](const Call& k) {
+                              return sts_ar_fit_remove(k.in(0), k.out(1), k.n, T, k.ld, k.ld, p, no_intercept, k.out(2),
+                                                       k.out(3), k.err(4), k.st);
                           });
     return eo.finish(st, S, "ar_fit_remove");
 }
 
 int sts_garch_fit_host(const double* in, int64_t S, int64_t T, int64_t ld, double* params, int32_t* err) {
-    if (ld < T || (S > 0 && (!params || (T > 0 && !in)))) return sts_garch_fit(in, S, T, ld, params, nullptr, nullptr);
-    const size_t row = (size_t)(T > 0 ? T : 0) * sizeof(double);
     ErrOut eo(err, S);
-    const int st = staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(params, 3 * sizeof(double), 3 * sizeof(double)),
-                              out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
-                          [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                              return sts_garch_fit(static_cast<const double*>(d[0]), n, T, T, static_cast<double*>(d[1]),
-                                                   static_cast<int32_t*>(d[2]), s);
-                          });
+    const int st = staged(S, T, ld, {in_panel(in), out_vec(params, 3), status(eo)}, [&](const Call& c) {
+        return sts_garch_fit(c.in(0), c.n, T, c.ld, c.out(1), c.err(2), c.st);
+    });
     return eo.finish(st, S, "GARCH.fitModel");
 }
 
 int sts_argarch_fit_host(const double* in, int64_t S, int64_t T, int64_t ld, double* c, double* phi, double* params,
                          int32_t* err) {
-    if (ld < T || T - 1 < 2 || (S > 0 && (!c || !phi || !params || !in)))
-        return sts_argarch_fit(in, S, T, ld, c, phi, params, nullptr, nullptr);
-    const size_t row = (size_t)T * sizeof(double);
     ErrOut eo(err, S);
-    const int st = staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(c, sizeof(double), sizeof(double)),
-                              out_arg(phi, sizeof(double), sizeof(double)),
-                              out_arg(params, 3 * sizeof(double), 3 * sizeof(double)),
-                              out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
-                          [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                              return sts_argarch_fit(static_cast<const double*>(d[0]), n, T, T,
-                                                     static_cast<double*>(d[1]), static_cast<double*>(d[2]),
-                                                     static_cast<double*>(d[3]), static_cast<int32_t*>(d[4]), s);
+    const int st = staged(S, T, ld, {in_panel(in), out_vec(c), out_vec(phi), out_vec(params, 3), status(eo)},
+                          [&](const Call& k) {
+                              return sts_argarch_fit(k.in(0), k.n, T, k.ld, k.out(1), k.out(2), k.out(3), k.err(4),
+                                                     k.st);
                           });
     return eo.finish(st, S, "ARGARCH.fitModel");
 }
 
-static int ar_host(bool add, const double* in, double* out, int64_t S, int64_t T, int64_t ld, const double* c,
-                   const double* coef, int p) {
-    auto dev_call = [&](const double* i, double* o, int64_t n, const double* cc, const double* k, hipStream_t s) {
-        return add ? sts_ar_add(i, o, n, T, T, T, cc, k, p, s) : sts_ar_remove(i, o, n, T, T, T, cc, k, p, s);
-    };
-    if (!out || ld < T || p < 0 || (S > 0 && (!c || (p > 0 && !coef))) || (S * T > 0 && !in))
-        return add ? sts_ar_add(in, out, S, T, ld, ld, c, coef, p, nullptr)
-                   : sts_ar_remove(in, out, S, T, ld, ld, c, coef, p, nullptr);
-    if (S * T == 0) return STS_OK;
-    const size_t row = (size_t)T * sizeof(double), prow = (size_t)(p > 0 ? p : 1) * sizeof(double);
+static int ar_host(decltype(&sts_ar_add) fn, const double* in, double* out, int64_t S, int64_t T, int64_t ld,
+                   const double* c, const double* coef, int p) {
+    // not an argument check: p = 0 has no coefficients (coef may be NULL), but the recurrence kernels
+    // still load one per series, so one zero stands in for every series' row (host stride 0)
     const double zero = 0.0;
-    const double* k = p > 0 ? coef : &zero;
-    const size_t kst = p > 0 ? prow : 0;   // (p = 0: no coefficients; a dummy row)
-    if (in == out)
-        return staged(S, {inout_arg(out, row, panel_stride(ld)), in_arg(c, sizeof(double), sizeof(double)),
-                          in_arg(k, prow, kst)},
-                      [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                          return dev_call(static_cast<double*>(d[0]), static_cast<double*>(d[0]), n,
-                                          static_cast<const double*>(d[1]), static_cast<const double*>(d[2]), s);
-                      });
-    return staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(out, row, panel_stride(ld)),
-                      in_arg(c, sizeof(double), sizeof(double)), in_arg(k, prow, kst)},
-                  [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                      return dev_call(static_cast<const double*>(d[0]), static_cast<double*>(d[1]), n,
-                                      static_cast<const double*>(d[2]), static_cast<const double*>(d[3]), s);
-                  });
+    const Arg k = p > 0 ? in_vec(coef, p) : in_arg(&zero, sizeof(double), 0);
+    return staged(S, T, ld, {in_panel(in), out_panel(out), in_vec(c), k}, [&](const Call& a) {
+        return fn(a.in(0), a.out(1), a.n, T, a.ld, a.ld, a.in(2), a.in(3), p, a.st);
+    });
 }
 
 int sts_ar_remove_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, const double* c,
                        const double* coef, int p) {
-    return ar_host(false, in, out, S, T, ld, c, coef, p);
+    return ar_host(sts_ar_remove, in, out, S, T, ld, c, coef, p);
 }
 
 int sts_ar_add_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, const double* c,
                     const double* coef, int p) {
-    return ar_host(true, in, out, S, T, ld, c, coef, p);
+    return ar_host(sts_ar_add, in, out, S, T, ld, c, coef, p);
 }
 
-// ---- statistical tests: every other argument error comes from staged()'s validate-only call of
-// the device entry point ----
+// ---- statistical tests ----
 
 int sts_dw_test_host(const double* in, int64_t S, int64_t T, int64_t ld, double* stat) {
-    if (ld < T || T < 1 || (S > 0 && !in)) return sts_dw_test(in, S, T, ld, stat, nullptr);
-    const size_t row = (size_t)T * sizeof(double);
-    return staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(stat, sizeof(double), sizeof(double))},
-                  [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                      return sts_dw_test(static_cast<const double*>(d[0]), n, T, T, static_cast<double*>(d[1]), s);
-                  });
+    return staged(S, T, ld, {in_panel(in), out_vec(stat)}, [&](const Call& c) {
+        return sts_dw_test(c.in(0), c.n, T, c.ld, c.out(1), c.st);
+    });
 }
 
 int sts_kpss_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int regression, double* stat) {
-    if (ld < T || T < 1 || (S > 0 && !in)) return sts_kpss_test(in, S, T, ld, regression, stat, nullptr);
-    const size_t row = (size_t)T * sizeof(double);
-    return staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(stat, sizeof(double), sizeof(double))},
-                  [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                      return sts_kpss_test(static_cast<const double*>(d[0]), n, T, T, regression,
-                                           static_cast<double*>(d[1]), s);
-                  });
+    return staged(S, T, ld, {in_panel(in), out_vec(stat)}, [&](const Call& c) {
+        return sts_kpss_test(c.in(0), c.n, T, c.ld, regression, c.out(1), c.st);
+    });
 }
 
 int sts_adf_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag, int regression, double* stat,
                       double* pvalue, int32_t* err) {
-    if (ld < T || T < 1 || (S > 0 && !in))
-        return sts_adf_test(in, S, T, ld, max_lag, regression, stat, pvalue, nullptr, nullptr);
-    const size_t row = (size_t)T * sizeof(double);
     ErrOut eo(err, S);
-    const int st = staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(stat, sizeof(double), sizeof(double)),
-                              out_arg(pvalue, sizeof(double), sizeof(double)),
-                              out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
-                          [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                              return sts_adf_test(static_cast<const double*>(d[0]), n, T, T, max_lag, regression,
-                                                  static_cast<double*>(d[1]),
-                                                  pvalue ? static_cast<double*>(d[2]) : nullptr,
-                                                  static_cast<int32_t*>(d[3]), s);
-                          });
+    const int st = staged(S, T, ld, {in_panel(in), out_vec(stat), out_vec(pvalue), status(eo)}, [&](const Call& c) {
+        return sts_adf_test(c.in(0), c.n, T, c.ld, max_lag, regression, c.out(1), c.out(2), c.err(3), c.st);
+    });
     return eo.finish(st, S, "adftest");
 }
 
 int sts_lb_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag, double* stat, double* pvalue) {
-    if (ld < T || T < 1 || (S > 0 && !in)) return sts_lb_test(in, S, T, ld, max_lag, stat, pvalue, nullptr);
-    const size_t row = (size_t)T * sizeof(double);
-    return staged(S, {in_arg(in, row, panel_stride(ld)), out_arg(stat, sizeof(double), sizeof(double)),
-                      out_arg(pvalue, sizeof(double), sizeof(double))},
-                  [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                      return sts_lb_test(static_cast<const double*>(d[0]), n, T, T, max_lag, static_cast<double*>(d[1]),
-                                         pvalue ? static_cast<double*>(d[2]) : nullptr, s);
-                  });
+    return staged(S, T, ld, {in_panel(in), out_vec(stat), out_vec(pvalue)}, [&](const Call& c) {
+        return sts_lb_test(c.in(0), c.n, T, c.ld, max_lag, c.out(1), c.out(2), c.st);
+    });
 }
 
 // bgtest / bptest: a shared factor matrix (fs == 0) is copied to the device once, row by row (only
@@ -738,15 +658,17 @@ static int bgbp_host(bool bp, const double* resid, int64_t S, int64_t T, int64_t
         return bp ? sts_bp_test(e, n, T, lde, f, k, ldf, fsf, st, pv, er, s)
                   : sts_bg_test(e, n, T, lde, f, k, ldf, fsf, max_lag, st, pv, er, s);
     };
-    // every argument error first, on the caller's shapes: nothing is staged or copied on bad input
-    int r = sts::validate([&] { return dev_call(resid, S, ld, factors, ld_f, fs, stat, pvalue, nullptr, nullptr); });
-    if (r) return r;
-    if (S <= 0) return STS_OK;
+    // a validation of this wrapper's own, ahead of staged()'s: the sizes below (k rows, the factor
+    // span) must not overflow, and shared factors are uploaded before the pipeline runs -- nothing is
+    // copied on bad input
+    bool work = false;
+    const int r = sts::validate(
+        [&] { return dev_call(resid, S, ld, factors, ld_f, fs, stat, pvalue, nullptr, nullptr); }, &work);
+    if (r || !work) return r;
     const size_t row = (size_t)T * sizeof(double);
-    ErrOut eo(err, S);
-    int st;
-    if (fs == 0) {
-        void* df = nullptr;
+    const int64_t span = (int64_t)(k - 1) * ld_f + T;
+    void* df = nullptr;
+    if (fs == 0) {   // picks the code path: shared factors, once, outside the pipeline
         hipError_t e = hipMalloc(&df, (size_t)k * row);
         if (e != hipSuccess) return hip_status(e, "hipMalloc(factors)");
         e = hipMemcpy2D(df, row, factors, (size_t)ld_f * sizeof(double), row, (size_t)k, hipMemcpyHostToDevice);
@@ -754,28 +676,18 @@ static int bgbp_host(bool bp, const double* resid, int64_t S, int64_t T, int64_t
             (void)hipFree(df);
             return hip_status(e, "hipMemcpy2D(factors)");
         }
-        st = staged(S, {in_arg(resid, row, panel_stride(ld)), out_arg(stat, sizeof(double), sizeof(double)),
-                        out_arg(pvalue, sizeof(double), sizeof(double)), out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
-                    [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                        if (!s) return (int)STS_OK;   // validated above (the factors are on the device by now)
-                        return dev_call(static_cast<const double*>(d[0]), n, T, static_cast<const double*>(df), T, 0,
-                                        static_cast<double*>(d[1]), pvalue ? static_cast<double*>(d[2]) : nullptr,
-                                        static_cast<int32_t*>(d[3]), s);
-                    });
-        (void)hipFree(df);   // every chunk is back
-    } else {
-        const int64_t span = (int64_t)(k - 1) * ld_f + T;
-        st = staged(S, {in_arg(resid, row, panel_stride(ld)),
-                        in_arg(factors, (size_t)span * sizeof(double), (size_t)fs * sizeof(double)),
-                        out_arg(stat, sizeof(double), sizeof(double)), out_arg(pvalue, sizeof(double), sizeof(double)),
-                        out_arg(eo.h, sizeof(int32_t), sizeof(int32_t))},
-                    [&](void* const* d, int64_t, int64_t n, hipStream_t s) {
-                        if (!s) return (int)STS_OK;
-                        return dev_call(static_cast<const double*>(d[0]), n, T, static_cast<const double*>(d[1]), ld_f,
-                                        span, static_cast<double*>(d[2]), pvalue ? static_cast<double*>(d[3]) : nullptr,
-                                        static_cast<int32_t*>(d[4]), s);
-                    });
     }
+    // what the device call is given as factors: the uploaded copy (packed rows), or the chunk's own
+    // blocks (during validation the caller's, at a stride the check above accepted)
+    const Arg own = fs == 0 ? Arg() : in_arg(factors, (size_t)span * sizeof(double), (size_t)fs * sizeof(double));
+    ErrOut eo(err, S);
+    const int st = staged(S, T, ld, {in_panel(resid), own, out_vec(stat), out_vec(pvalue), status(eo)},
+                          [&](const Call& c) {
+                              const double* f = fs == 0 ? static_cast<const double*>(df) : c.in(1);
+                              return dev_call(c.in(0), c.n, c.ld, f, fs == 0 ? T : ld_f, fs == 0 ? 0 : span, c.out(2),
+                                              c.out(3), c.err(4), c.st);
+                          });
+    if (df) (void)hipFree(df);   // every chunk is back
     return eo.finish(st, S, bp ? "bptest" : "bgtest");
 }
 

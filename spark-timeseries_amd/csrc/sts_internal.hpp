@@ -68,11 +68,14 @@ int series_status(const int32_t* h, int64_t S, const char* what);
 int set_error(int status, const char* msg);
 // Run fn(ctx) -- a call of a device entry point -- in validate-only mode: the entry point
 // checks its arguments and returns their status, stopping at its first device action.
-// The `_host` entry points validate this way before staging anything.
-int validate_call(int (*fn)(void*), void* ctx);
+// *has_work says whether it got that far: false with STS_OK means the entry point returned
+// before any device action (an empty panel, lag 0), so the call has nothing to do.
+// Every `_host` entry point validates this way -- its own device call, on the caller's pointers,
+// shapes and ld -- before staging anything, and stages nothing without work (sts_host.cpp staged()).
+int validate_call(int (*fn)(void*), void* ctx, bool* has_work);
 template <class F>
-int validate(F&& f) {
-    return validate_call([](void* c) { return (*static_cast<F*>(c))(); }, static_cast<void*>(&f));
+int validate(F&& f, bool* has_work) {
+    return validate_call([](void* c) { return (*static_cast<F*>(c))(); }, static_cast<void*>(&f), has_work);
 }
 
 // launchers (return hipError_t of the launch)

@@ -870,8 +870,76 @@ def _host_garch(H, x, a, ld):
     assert_bits(par.data().reshape(HOST_S, 3), rpar, "argarch_fit_host")
 
 
+def _ar_remove_in_place(r, c, coef):
+    """dest eq ts: ts(i - j - 1) is already dest(i - j - 1) (the recurrence test_recur_shapes.py builds)"""
+    r = r.copy()
+    for i in range(r.size):
+        v = r[i] - c
+        for j in range(min(len(coef), i)):
+            v -= r[i - j - 1] * coef[j]
+        r[i] = v
+    return r
+
+
+def _dest_is_ts(fn, r, *model):
+    """an oracle recurrence with dest = ts, on a copy of the row"""
+    r = r.copy()
+    fn(r, *model, dest=r)
+    return r
+
+
+def _host_in_place(H, x, a, ld):
+    # in == out: one device region per chunk for both, copied in and copied out from there
+    p = 3
+    sm = np.linspace(0.1, 0.9, HOST_S)
+    cm, cf = np.linspace(-1, 1, HOST_S), np.linspace(-0.3, 0.3, HOST_S * p).reshape(HOST_S, p)
+    rows = range(HOST_S)
+    for name, fn, tail, ref in (
+            ("diff_at_lag_host", lib().sts_diff_at_lag_host, (3, 7),
+             [oracle.differences_at_lag(r.copy(), 3, start=7, inplace=True) for r in x]),
+            ("ewma_add_host", lib().sts_ewma_add_host, (P(sm),), [_dest_is_ts(oracle.ewma_add, x[s], sm[s]) for s in rows]),
+            ("ewma_remove_host", lib().sts_ewma_remove_host, (P(sm),),
+             [_dest_is_ts(oracle.ewma_remove, x[s], sm[s]) for s in rows]),
+            ("ar_add_host", lib().sts_ar_add_host, (P(cm), P(cf), p),
+             [oracle.ar_add(x[s].copy(), cm[s], cf[s], inplace=True) for s in rows]),
+            ("ar_remove_host", lib().sts_ar_remove_host, (P(cm), P(cf), p),
+             [_ar_remove_in_place(x[s], cm[s], cf[s]) for s in rows])):
+        io = H.carve(HOST_S, HOST_T, ld, la.OUT_FILL, data=x)
+        run_host(name + " in place", fn, (io.ptr, io.ptr, HOST_S, HOST_T, ld) + tail, [], [io])
+        assert_bits(io.data(), np.array(ref), name + " in place")
+
+
+def _host_optional(H, x, a, ld):
+    # pvalue == NULL stays NULL on the device: the statistic is the one of the call with a p-value array
+    for name, fn, head, tail in (("adf_test_host", lib().sts_adf_test_host, (2, 1), (None,)),
+                                 ("lb_test_host", lib().sts_lb_test_host, (5,), ())):
+        got = []
+        for with_p in (True, False):
+            stat, pv = H.vec(HOST_S), H.vec(HOST_S)
+            outs = [stat, pv] if with_p else [stat]
+            run_host(name, fn, (a.ptr, HOST_S, HOST_T, ld) + head + (stat.ptr, pv.ptr if with_p else None) + tail,
+                     [a], outs)
+            got.append(stat.data().copy())
+            assert np.isfinite(got[-1]).all(), name
+            if with_p:
+                p = pv.data().ravel()
+                assert ((p >= 0) & (p <= 1)).all(), (name, p)
+        assert_bits(got[1], got[0], name + " without pvalue")
+
+
+def _host_ar_p0(H, x, a, ld):
+    # p = 0: no coefficients, coef == NULL (the wrapper's dummy coefficient row)
+    cm = np.linspace(-1, 1, HOST_S)
+    for name, fn, orc in (("ar_remove_host", lib().sts_ar_remove_host, oracle.ar_remove),
+                          ("ar_add_host", lib().sts_ar_add_host, oracle.ar_add)):
+        o = H.carve(HOST_S, HOST_T, ld, la.OUT_FILL)
+        run_host(name + " p = 0", fn, (a.ptr, o.ptr, HOST_S, HOST_T, ld, P(cm), None, 0), [a], [o])
+        assert_bits(o.data(), np.array([orc(x[s], cm[s], []) for s in range(HOST_S)]), name + " p = 0")
+
+
 HOST_OPS = {"autocorr": _host_autocorr, "diff_at_lag": _host_diff, "lag_matrix": _host_lag, "ewma": _host_ewma,
-            "ar": _host_ar, "garch": _host_garch}
+            "ar": _host_ar, "garch": _host_garch, "in_place": _host_in_place, "optional_outputs": _host_optional,
+            "ar_p0": _host_ar_p0}
 
 
 @pytest.mark.parametrize("pinned", [False, True], ids=["pageable", "pinned"])
