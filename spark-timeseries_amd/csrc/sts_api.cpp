@@ -1398,6 +1398,194 @@ int sts_fill_diff_ewma(const double* in, double* out, int64_t S, int64_t T, int6
     return es.finish("fill_diff_ewma");
 }
 
+// ---- panel transforms: include/sts_transforms.h (sts_transforms.hip, sts_recur.hip) ----
+
+int sts_quotients(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int lag,
+                  int minus_one, void* stream) {
+    int r;
+    if ((r = check_panel(in, S, T, ld_in, "quotients"))) return r;
+    if (lag < 0 || lag > T) return fail(STS_ERR_BAD_ARG, "quotients: lag %d outside [0, T=%lld]", lag, (long long)T);
+    if ((r = check_panel(out, S, T - lag, ld_out, "quotients"))) return r;
+    if (S * (T - lag) == 0) return STS_OK;   // lag == T: an empty vector
+    if (in == out) return fail(STS_ERR_BAD_ARG, "quotients: out must not alias in");
+    if ((r = ensure_device())) return r;
+    HIP_TRY(sts::launch_quotients(in, out, S, T, ld_in, ld_out, lag, minus_one != 0, as_stream(stream)), "quotients");
+    return STS_OK;
+}
+
+int sts_fill_quotients(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int method,
+                       int lag, int minus_one, int32_t* err_per_series, void* stream) {
+    int r;
+    if ((r = method_ok(method, true, "fill_quotients"))) return r;
+    if ((r = check_panel(in, S, T, ld_in, "fill_quotients"))) return r;
+    if (lag < 0 || lag > T) return fail(STS_ERR_BAD_ARG, "fill_quotients: lag %d outside [0, T=%lld]", lag, (long long)T);
+    if ((r = check_panel(out, S, T - lag, ld_out, "fill_quotients"))) return r;
+    if (S * (T - lag) > 0 && in == out) return fail(STS_ERR_BAD_ARG, "fill_quotients: out must not alias in");
+    if (S == 0) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    ErrSink es(err_per_series, S, st);
+    const bool m1 = minus_one != 0;
+    if (method == STS_FILL_NONE) {   // r1 itself; no series can fail
+        if ((r = es.prepare())) return r;
+        HIP_TRY(sts::launch_quotients(in, out, S, T, ld_in, ld_out, lag, m1, st), "quotients");
+        return es.finish("fill_quotients");
+    }
+    if (method == STS_FILL_PREVIOUS && lag >= 1 && lag <= sts::kFillQuotMaxLag) {
+        // one pass: fillPrevious has no failing series, and its filled values never leave the wave
+        if ((r = es.prepare())) return r;
+        HIP_TRY(timed(st, [&] { return sts::launch_fill_prev_quotients(in, out, S, T, ld_in, ld_out, lag, m1, st); }),
+                "fill_quotients");
+        return es.finish("fill_quotients");
+    }
+    // composition: fill (a fresh vector) into scratch rows of even pitch, so the fill's 16-byte
+    // store forms apply whatever T is, then r1 on it.  The fill runs for lag == T too: its
+    // per-series statuses are part of the result.
+    if ((r = es.prepare(false))) return r;   // run_tile zeroes err unless its kernel writes all of it
+    const int64_t ldf = (T + 1) & ~(int64_t)1;
+    Scratch tmp(st);
+    HIP_TRY(tmp.alloc((size_t)(S * ldf) * sizeof(double)), "hipMallocAsync(filled)");
+    double* f = static_cast<double*>(tmp.p);
+    if ((r = run_tile(in, f, nullptr, S, T, ld_in, ldf, method, 0, nullptr, 0, 0, es.dev, st, "fill"))) return r;
+    HIP_TRY(sts::launch_quotients(f, out, S, T, ldf, ld_out, lag, m1, st), "quotients");
+    return es.finish("fill_quotients");
+}
+
+int sts_fill_with_default(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out,
+                          double filler, void* stream) {
+    int r;
+    if ((r = check_panel(in, S, T, ld_in, "fillWithDefault"))) return r;
+    if ((r = check_panel(out, S, T, ld_out, "fillWithDefault"))) return r;
+    if (S * T == 0) return STS_OK;
+    if (in == out && ld_in != ld_out) return fail(STS_ERR_BAD_ARG, "fillWithDefault: in-place call with different ld");
+    if ((r = ensure_device())) return r;
+    HIP_TRY(sts::launch_fill_default(in, out, S, T, ld_in, ld_out, filler, as_stream(stream)), "fillWithDefault");
+    return STS_OK;
+}
+
+int sts_downsample(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int n, int phase,
+                   void* stream) {
+    int r;
+    if ((r = check_panel(in, S, T, ld_in, "downsample"))) return r;
+    if (n < 1) return fail(STS_ERR_BAD_ARG, "downsample: n = %d must be at least 1", n);
+    if (phase < 0) return fail(STS_ERR_BAD_ARG, "downsample: negative phase %d", phase);
+    const int64_t To = phase >= T ? 0 : (T - phase + n - 1) / n;   // ceil((T - phase) / n)
+    if ((r = check_panel(out, S, To, ld_out, "downsample"))) return r;
+    if (S * To == 0) return STS_OK;
+    if (in == out) return fail(STS_ERR_BAD_ARG, "downsample: out must not alias in");
+    if ((r = ensure_device())) return r;
+    HIP_TRY(sts::launch_downsample(in, out, S, To, ld_in, ld_out, n, phase, as_stream(stream)), "downsample");
+    return STS_OK;
+}
+
+int sts_upsample(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int n, int phase,
+                 int use_zero, void* stream) {
+    int r;
+    if ((r = check_panel(in, S, T, ld_in, "upsample"))) return r;
+    if (n < 1) return fail(STS_ERR_BAD_ARG, "upsample: n = %d must be at least 1", n);
+    if (phase < 0 || phase >= n)
+        return fail(STS_ERR_BAD_ARG, "upsample: phase %d outside [0, n=%d): the last value would land past the array",
+                    phase, n);
+    if ((r = check_panel(out, S, T * n, ld_out, "upsample"))) return r;   // T * n within the Int range too
+    if (S * T == 0) return STS_OK;
+    if (in == out) return fail(STS_ERR_BAD_ARG, "upsample: out must not alias in");
+    if ((r = ensure_device())) return r;
+    HIP_TRY(sts::launch_upsample(in, out, S, T * n, ld_in, ld_out, n, phase, use_zero ? 0.0 : (double)NAN,
+                                 as_stream(stream)), "upsample");
+    return STS_OK;
+}
+
+int sts_first_last_not_nan(const double* in, int64_t S, int64_t T, int64_t ld, int64_t* first, int64_t* last,
+                           void* stream) {
+    int r;
+    if ((r = check_panel(in, S, T, ld, "firstNotNaN"))) return r;
+    if (S == 0 || (!first && !last)) return STS_OK;
+    if ((r = ensure_device())) return r;
+    HIP_TRY(sts::launch_first_last(in, S, T, ld, first, last, as_stream(stream)), "firstNotNaN / lastNotNaN");
+    return STS_OK;
+}
+
+int sts_inverse_diff_at_lag(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int lag,
+                            int start, void* stream) {
+    int r;
+    if (!(start >= lag)) return fail(STS_ERR_REQUIREMENT, "requirement failed: starting index cannot be less than lag");
+    if (lag < 0) return fail(STS_ERR_BAD_ARG, "inverseDifferencesAtLag: negative lag %d", lag);
+    if ((r = check_panel(in, S, T, ld_in, "inverseDifferencesAtLag"))) return r;
+    if ((r = check_panel(out, S, T, ld_out, "inverseDifferencesAtLag"))) return r;
+    if (lag == 0 || S * T == 0) return STS_OK;  // dest returned untouched (:404-405)
+    if (in == out && ld_in != ld_out)
+        return fail(STS_ERR_BAD_ARG, "inverseDifferencesAtLag: in-place call with different ld");
+    if ((r = ensure_device())) return r;
+    sts::RecurArgs a{};
+    a.in = in; a.out = out; a.S = S; a.T = T; a.ld_in = ld_in; a.ld_out = ld_out; a.lag = lag; a.start = start;
+    HIP_TRY(sts::launch_recur(sts::kInvDiffAtLag, a, as_stream(stream)), "inverseDifferencesAtLag");
+    return STS_OK;
+}
+
+// differencesOfOrderD / inverseDifferencesOfOrderD: d <= kOrderDOnePass in one pass (one register
+// per level), larger d as the reference's d sweeps
+static int order_d(bool inverse, const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out,
+                   int d, void* stream) {
+    const char* name = inverse ? "inverseDifferencesOfOrderD" : "differencesOfOrderD";
+    int r;
+    if (d < 0) return fail(STS_ERR_BAD_ARG, "%s: negative order %d", name, d);
+    if ((r = check_panel(in, S, T, ld_in, name))) return r;
+    if ((r = check_panel(out, S, T, ld_out, name))) return r;
+    if (S * T == 0) return STS_OK;
+    if (in == out) return fail(STS_ERR_BAD_ARG, "%s: out must not alias in (the reference returns a copy)", name);
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    if (d > T) d = (int)T;   // a sweep whose start index is past the end copies every element
+    if (d == 0) {
+        HIP_TRY(hipMemcpy2DAsync(out, ld_out * sizeof(double), in, ld_in * sizeof(double), T * sizeof(double), S,
+                                 hipMemcpyDeviceToDevice, st), name);
+        return STS_OK;
+    }
+    sts::RecurArgs a{};
+    a.in = in; a.out = out; a.S = S; a.T = T; a.ld_in = ld_in; a.ld_out = ld_out;
+    if (d <= sts::kOrderDOnePass) {
+        a.p = d;
+        HIP_TRY(sts::launch_recur(inverse ? sts::kInvDiffOrderD : sts::kDiffOrderD, a, st), name);
+        return STS_OK;
+    }
+    if (inverse) {   // addedTs = diffedTs.copy, then the sweeps i = d..1 in place
+        HIP_TRY(hipMemcpy2DAsync(out, ld_out * sizeof(double), in, ld_in * sizeof(double), T * sizeof(double), S,
+                                 hipMemcpyDeviceToDevice, st), name);
+        a.in = out; a.ld_in = ld_out; a.lag = 1;
+        for (int i = d; i >= 1; i--) {
+            a.start = i;
+            HIP_TRY(sts::launch_recur(sts::kInvDiffAtLag, a, st), name);
+        }
+        return STS_OK;
+    }
+    // the reference's ping-pong: sweep i reads the buffer sweep i - 1 wrote; the last one writes out
+    const int64_t ldf = (T + 1) & ~(int64_t)1;
+    Scratch tmp(st);
+    HIP_TRY(tmp.alloc((size_t)(S * ldf) * sizeof(double)), "hipMallocAsync(order-d scratch)");
+    double* f = static_cast<double*>(tmp.p);
+    const double* src = in;
+    int64_t ld_src = ld_in;
+    for (int i = 1; i <= d; i++) {
+        const bool to_out = (d - i) % 2 == 0;
+        double* dst = to_out ? out : f;
+        const int64_t ld_dst = to_out ? ld_out : ldf;
+        HIP_TRY(sts::launch_diff(src, dst, S, T, ld_src, ld_dst, 1, i, st), name);
+        src = dst;
+        ld_src = ld_dst;
+    }
+    return STS_OK;
+}
+
+int sts_diff_order_d(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int d,
+                     void* stream) {
+    return order_d(false, in, out, S, T, ld_in, ld_out, d, stream);
+}
+
+int sts_inverse_diff_order_d(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int d,
+                             void* stream) {
+    return order_d(true, in, out, S, T, ld_in, ld_out, d, stream);
+}
+
 // ---- statistical tests: S/stats/TimeSeriesStatisticalTests.scala (sts_stattests.hip) ----
 
 int sts_regression_from_name(const char* name) {

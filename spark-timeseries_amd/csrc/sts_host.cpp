@@ -701,4 +701,76 @@ int sts_bg_test_host(const double* resid, int64_t S, int64_t T, int64_t ld, cons
     return bgbp_host(false, resid, S, T, ld, factors, k, ld_f, fs, max_lag, stat, pvalue, err);
 }
 
+// ---- panel transforms (include/sts_transforms.h).  An output of another width than the input is
+// packed (out_vec): the width is computed here, for the staging size alone and only for a shape the
+// device entry point accepts (so it cannot overflow); every other shape gets width 0 and the entry
+// point's own message. ----
+
+int sts_quotients_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int lag, int minus_one) {
+    const int64_t n = (lag >= 0 && lag <= T) ? T - lag : 0;
+    return staged(S, T, ld, {in_panel(in), out_vec(out, n)}, [&](const Call& c) {
+        return sts_quotients(c.in(0), c.out(1), c.n, T, c.ld, n, lag, minus_one, c.st);
+    });
+}
+
+int sts_fill_quotients_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int method, int lag,
+                            int minus_one, int32_t* err) {
+    const int64_t n = (lag >= 0 && lag <= T) ? T - lag : 0;
+    ErrOut eo(err, S);
+    const int st = staged(S, T, ld, {in_panel(in), out_vec(out, n), status(eo)}, [&](const Call& c) {
+        return sts_fill_quotients(c.in(0), c.out(1), c.n, T, c.ld, n, method, lag, minus_one, c.err(2), c.st);
+    });
+    return eo.finish(st, S, "fill_quotients");
+}
+
+// in == out: element-wise, safe
+int sts_fill_with_default_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, double filler) {
+    return staged(S, T, ld, {in_panel(in), out_panel(out)}, [&](const Call& c) {
+        return sts_fill_with_default(c.in(0), c.out(1), c.n, T, c.ld, c.ld, filler, c.st);
+    });
+}
+
+int sts_downsample_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int n, int phase) {
+    const bool sized = n >= 1 && phase >= 0 && phase < T && T <= 0x7fffffffLL;
+    const int64_t w = sized ? (T - phase + n - 1) / n : 0;
+    return staged(S, T, ld, {in_panel(in), out_vec(out, w)}, [&](const Call& c) {
+        return sts_downsample(c.in(0), c.out(1), c.n, T, c.ld, w, n, phase, c.st);
+    });
+}
+
+int sts_upsample_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int n, int phase, int use_zero) {
+    const bool sized = n >= 1 && T >= 0 && T <= 0x7fffffffLL && T * n <= 0x7fffffffLL;
+    const int64_t w = sized ? T * n : 0;
+    return staged(S, T, ld, {in_panel(in), out_vec(out, w)}, [&](const Call& c) {
+        return sts_upsample(c.in(0), c.out(1), c.n, T, c.ld, sized ? w : T * (int64_t)n, n, phase, use_zero, c.st);
+    });
+}
+
+int sts_first_last_not_nan_host(const double* in, int64_t S, int64_t T, int64_t ld, int64_t* first, int64_t* last) {
+    return staged(S, T, ld, {in_panel(in), out_arg(first, sizeof(int64_t), sizeof(int64_t)),
+                             out_arg(last, sizeof(int64_t), sizeof(int64_t))}, [&](const Call& c) {
+        return sts_first_last_not_nan(c.in(0), c.n, T, c.ld, static_cast<int64_t*>(c.at(1)),
+                                      static_cast<int64_t*>(c.at(2)), c.st);
+    });
+}
+
+// in == out gives the same bits as out of place (history of outputs); lag 0 leaves dest untouched
+int sts_inverse_diff_at_lag_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int lag, int start) {
+    return staged(S, T, ld, {in_panel(in), out_panel(out)}, [&](const Call& c) {
+        return sts_inverse_diff_at_lag(c.in(0), c.out(1), c.n, T, c.ld, c.ld, lag, start, c.st);
+    });
+}
+
+int sts_diff_order_d_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int d) {
+    return staged(S, T, ld, {in_panel(in), out_panel(out)}, [&](const Call& c) {
+        return sts_diff_order_d(c.in(0), c.out(1), c.n, T, c.ld, c.ld, d, c.st);
+    });
+}
+
+int sts_inverse_diff_order_d_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int d) {
+    return staged(S, T, ld, {in_panel(in), out_panel(out)}, [&](const Call& c) {
+        return sts_inverse_diff_order_d(c.in(0), c.out(1), c.n, T, c.ld, c.ld, d, c.st);
+    });
+}
+
 }  // extern "C"

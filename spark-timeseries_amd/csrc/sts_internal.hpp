@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "sts.h"
+#include "sts_transforms.h"
 
 namespace sts {
 
@@ -128,7 +129,10 @@ hipError_t launch_ar_remove(const double* in, double* out, int64_t S, int64_t T,
 
 // series-per-lane recurrences (sts_recur.hip)
 enum RecurOp { kEwmaAdd = 0, kEwmaRemoveInplace = 1, kArAdd = 2, kArRemoveInplace = 3,
-               kFillDiffEwma = 4, kDiffInplace = 5 };
+               kFillDiffEwma = 4, kDiffInplace = 5,
+               // sts_transforms.h r6 / r7: history of OUTPUTS at `lag`; one previous value per level (p = d <= 8)
+               kInvDiffAtLag = 6, kDiffOrderD = 7, kInvDiffOrderD = 8 };
+constexpr int kOrderDOnePass = 8;   // largest d the one-pass order-d lanes hold (one register per level)
 struct RecurArgs {
     const double* in;
     double* out;
@@ -141,6 +145,24 @@ struct RecurArgs {
     int method;           // fill method for kFillDiffEwma
 };
 hipError_t launch_recur(RecurOp op, const RecurArgs& a, hipStream_t st);
+
+// panel transforms (sts_transforms.hip; include/sts_transforms.h r1-r5)
+hipError_t launch_quotients(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int lag,
+                            bool minus_one, hipStream_t st);
+// fillPrevious -> quotients in one pass, 1 <= lag <= kFillQuotMaxLag (one wave per series)
+constexpr int kFillQuotMaxLag = 32;
+hipError_t launch_fill_prev_quotients(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out,
+                                      int lag, bool minus_one, hipStream_t st);
+hipError_t launch_fill_default(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out,
+                               double filler, hipStream_t st);
+// out(s, j) = in(s, phase + j * n), j < T_out
+hipError_t launch_downsample(const double* in, double* out, int64_t S, int64_t T_out, int64_t ld_in, int64_t ld_out, int n,
+                             int phase, hipStream_t st);
+// out(s, i), i < T_out = T * n: in(s, (i - phase) / n) on the grid, filler elsewhere
+hipError_t launch_upsample(const double* in, double* out, int64_t S, int64_t T_out, int64_t ld_in, int64_t ld_out, int n,
+                           int phase, double filler, hipStream_t st);
+hipError_t launch_first_last(const double* in, int64_t S, int64_t T, int64_t ld, int64_t* first, int64_t* last,
+                             hipStream_t st);
 
 // AR fit (sts_ar.hip)
 struct ArArgs {

@@ -5,6 +5,8 @@
 //   ARModel.addTimeDependentEffects       S/models/Autoregression.scala:75-88 (IIR)
 //   ARModel.removeTimeDependentEffects    S/models/Autoregression.scala:60-73 (dest eq ts)
 //   differencesAtLag                      S/UnivariateTimeSeries.scala:356-376 (dest eq ts)
+//   inverseDifferencesAtLag               S/UnivariateTimeSeries.scala:397-417
+//   differencesOfOrderD / inverseDifferencesOfOrderD, d <= 8, every sweep in one pass  :438-465
 //   C2 pipeline fillPrevious -> differencesAtLag(lag) -> EWMA add, fused (one HBM pass)
 //
 // Two kernels:
@@ -51,7 +53,7 @@ struct RecurLane {
     // arithmetic on them, so nothing waits for them until finish()); finish: derived values
     __device__ __forceinline__ void load(const RecurArgs& a, int64_t sl, bool live) {
         carry = __builtin_nan("");
-        hp = (OP == kArAdd || OP == kArRemoveInplace) ? a.p : a.lag;   // history length used
+        hp = (OP == kArAdd || OP == kArRemoveInplace || OP == kDiffOrderD || OP == kInvDiffOrderD) ? a.p : a.lag;   // history length used
         start = (OP == kFillDiffEwma) ? a.lag : a.start;
         e = 0.0;
         const int64_t si = live ? sl : 0;
@@ -112,6 +114,34 @@ struct RecurLane {
 #pragma unroll
             for (int j = 0; j < H; j++) hl = (j == hp - 1) ? h[j] : hl;   // static indexing
             y = before ? x : x - hl;
+        } else if (OP == kInvDiffAtLag) {
+            // addedTs(i) = diffedTs(i) + addedTs(i - lag): h is the history of outputs (copies before start)
+            double hl = 0.0;
+#pragma unroll
+            for (int j = 0; j < H; j++) hl = (j == hp - 1) ? h[j] : hl;   // static indexing
+            y = before ? x : x + hl;
+        } else if (OP == kDiffOrderD) {
+            // sweep k + 1 = differencesAtLag(level k, _, 1, k + 1); h[k]: level k at t - 1.  The same
+            // subtractions in the same order as the reference's d sweeps over the ping-pong buffers.
+            double v = x;
+#pragma unroll
+            for (int k = 0; k < H; k++)
+                if (k < hp) {
+                    const double nv = (t < k + 1) ? v : v - h[k];
+                    h[k] = v;
+                    v = nv;
+                }
+            return v;
+        } else if (OP == kInvDiffOrderD) {
+            // sweeps i = d..1 of inverseDifferencesAtLag(a, a, 1, i); h[i - 1]: sweep i's output at t - 1
+            double v = x;
+#pragma unroll
+            for (int k = H - 1; k >= 0; k--)
+                if (k < hp) {
+                    v = (t < k + 1) ? v : v + h[k];
+                    h[k] = v;
+                }
+            return v;
         } else {  // kFillDiffEwma: fillPrevious -> differencesAtLag(lag, start=lag) -> EWMA add
             carry = (x != x) ? carry : x;
             const double f = carry;
@@ -467,6 +497,24 @@ __global__ __launch_bounds__(256) void diff_chain_kernel(double* x, int64_t S, i
         if (t >= start) v[t] = v[t] - v[t - lag];
 }
 
+// inverseDifferencesAtLag along the same chains: out of place or in place (a chain reads in(t)
+// before it writes out(t), and its own previous output from a register)
+__global__ __launch_bounds__(256) void inv_diff_chain_kernel(const double* in, double* out, int64_t S, int64_t T,
+                                                             int64_t ld_in, int64_t ld_out, int lag, int start) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= S * lag) return;
+    const int64_t s = g / lag;
+    const int r = (int)(g - s * lag);
+    const double* x = in + s * ld_in;
+    double* v = out + s * ld_out;
+    double prev = 0.0;
+    for (int64_t t = r; t < T; t += lag) {
+        const double y = (t < start) ? x[t] : x[t] + prev;
+        v[t] = y;
+        prev = y;
+    }
+}
+
 // AR add / in-place AR remove of order p > 32: one thread per series on global memory
 template <int OP>
 __global__ __launch_bounds__(256) void ar_naive_kernel(RecurArgs a) {
@@ -548,6 +596,9 @@ chunks:
     else if (OP == kDiffInplace)
         hipLaunchKernelGGL(diff_chain_kernel, dim3((unsigned)((a.S * a.lag + 255) / 256)), dim3(256), 0, st,
                            a.out, a.S, a.T, a.ld_out, a.lag, a.start);
+    else if (OP == kInvDiffAtLag)
+        hipLaunchKernelGGL(inv_diff_chain_kernel, dim3((unsigned)((a.S * a.lag + 255) / 256)), dim3(256), 0, st,
+                           a.in, a.out, a.S, a.T, a.ld_in, a.ld_out, a.lag, a.start);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -562,6 +613,9 @@ hipError_t launch_recur(RecurOp op, const RecurArgs& a, hipStream_t st) {
     case kArAdd: return launch_h<kArAdd>(a, a.p, st);
     case kArRemoveInplace: return launch_h<kArRemoveInplace>(a, a.p, st);
     case kDiffInplace: return launch_h<kDiffInplace>(a, a.lag, st);
+    case kInvDiffAtLag: return launch_h<kInvDiffAtLag>(a, a.lag, st);
+    case kDiffOrderD: return a.p > kOrderDOnePass ? hipErrorInvalidValue : launch_h<kDiffOrderD>(a, a.p, st);
+    case kInvDiffOrderD: return a.p > kOrderDOnePass ? hipErrorInvalidValue : launch_h<kInvDiffOrderD>(a, a.p, st);
     case kFillDiffEwma:
         return launch_h<kFillDiffEwma>(a, a.lag, st);
     }

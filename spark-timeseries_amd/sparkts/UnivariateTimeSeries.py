@@ -2,7 +2,7 @@
 
 Same function names, argument meaning and exceptions as the Scala object; every
 function accepts one series (T,) or a whole panel (S, T) and dispatches ONE batched
-C-ABI call (include/sts.h) -- torch GPU tensors take the device path on torch's
+C-ABI call (include/sts.h, include/sts_transforms.h) -- torch GPU tensors take the device path on torch's
 current stream, numpy arrays take the host-staging (`_host`) path.  Results are
 always fresh arrays, as in the reference.
 """
@@ -15,7 +15,9 @@ from ._panel import Panel, check, ptr
 from .errors import UnsupportedOperationException
 
 __all__ = ["fillts", "fillLinear", "fillNearest", "fillNext", "fillPrevious", "fillSpline", "autocorr", "lag",
-           "differencesAtLag", "ar", "fill_method_code"]
+           "differencesAtLag", "ar", "fill_method_code", "quotients", "price2ret", "fillWithDefault", "downsample",
+           "upsample", "firstNotNaN", "lastNotNaN", "trimLeading", "trimTrailing", "inverseDifferencesAtLag",
+           "differencesOfOrderD", "inverseDifferencesOfOrderD"]
 
 
 def fill_method_code(method: str) -> int:
@@ -113,6 +115,17 @@ def differencesAtLag(ts, lag: int, destTs=None, startIndex=None):
     destTs given the result is written there and returned; destTs may be ts itself,
     which reproduces the reference's in-place semantics (later elements see already
     differenced values)."""
+    return _at_lag("differencesAtLag", "sts_diff_at_lag", ts, lag, destTs, startIndex)
+
+
+def inverseDifferencesAtLag(diffedTs, lag: int, destTs=None, startIndex=None):
+    """S/UnivariateTimeSeries.scala:397-427: destTs(i) = diffedTs(i) + destTs(i - lag) from
+    startIndex (default lag) on, a copy before it.  destTs as in differencesAtLag; in place
+    (destTs is diffedTs) gives the same values."""
+    return _at_lag("inverseDifferencesAtLag", "sts_inverse_diff_at_lag", diffedTs, lag, destTs, startIndex)
+
+
+def _at_lag(what, fn, ts, lag, destTs, startIndex):
     start = lag if startIndex is None else startIndex
     p = Panel(ts)
     lib = _native.lib()
@@ -124,20 +137,18 @@ def differencesAtLag(ts, lag: int, destTs=None, startIndex=None):
     else:
         dp = Panel(destTs, "destTs")
         if dp.device != p.device or (dp.S, dp.T) != (p.S, p.T):
-            raise ValueError("differencesAtLag: destTs must be the same kind and shape as ts: (%d, %d) %s vs "
-                             "(%d, %d) %s" % (dp.S, dp.T, "device" if dp.device else "host", p.S, p.T,
+            raise ValueError("%s: destTs must be the same kind and shape as ts: (%d, %d) %s vs "
+                             "(%d, %d) %s" % (what, dp.S, dp.T, "device" if dp.device else "host", p.S, p.T,
                                               "device" if p.device else "host"))
         dview = p.t if destTs is ts else dp.t     # ts may have been made unit-stride: stay in place
         in_place_ptr = dview.data_ptr() == p.t.data_ptr() if p.device else dview.ctypes.data == p.t.ctypes.data
         dld = dp.ld
         dest = dview
     if p.device:
-        check(lib.sts_diff_at_lag(ptr(p.t), ptr(dview), p.S, p.T, p.ld,
-                                  p.ld if in_place_ptr else dld,
-                                  lag, start, p.stream), "differencesAtLag")
+        check(getattr(lib, fn)(ptr(p.t), ptr(dview), p.S, p.T, p.ld, p.ld if in_place_ptr else dld, lag, start,
+                               p.stream), what)
     else:
-        src = p.t
-        check(lib.sts_diff_at_lag_host(ptr(src), ptr(dview), p.S, p.T, p.ld, lag, start), "differencesAtLag")
+        check(getattr(lib, fn + "_host")(ptr(p.t), ptr(dview), p.S, p.T, p.ld, lag, start), what)
     if destTs is not None and p.device and dview.data_ptr() != destTs.data_ptr():
         # Panel made a unit-stride copy of a strided destTs: write the result back
         destTs.copy_(dview[0] if dp.squeeze else dview)
@@ -154,3 +165,119 @@ def ar(values, maxLag: int):
     """S/UnivariateTimeSeries.scala:299 -> Autoregression.fitModel(values, maxLag)."""
     from .models.Autoregression import Autoregression
     return Autoregression.fitModel(values, maxLag)
+
+
+def _resized(what, fn, ts, width, *args):
+    """one call of a transform whose output has `width` columns (packed): fn(in, out, S, T, ld_in,
+    ld_out, *args, stream) on the device, fn_host(in, out, S, T, ld, *args) on the host"""
+    p = Panel(ts)
+    w = width(p.T)
+    out = p.empty(T=max(w, 0))
+    lib = _native.lib()
+    if p.device:
+        check(getattr(lib, fn)(ptr(p.t), ptr(out), p.S, p.T, p.ld, max(w, 0), *args, p.stream), what)
+    else:
+        check(getattr(lib, fn + "_host")(ptr(p.t), ptr(out), p.S, p.T, p.ld, *args), what)
+    return p.out(out)
+
+
+def _same_shape(what, fn, ts, *args):
+    p = Panel(ts)
+    out = p.empty()
+    lib = _native.lib()
+    if p.device:
+        check(getattr(lib, fn)(ptr(p.t), ptr(out), p.S, p.T, p.ld, p.T, *args, p.stream), what)
+    else:
+        check(getattr(lib, fn + "_host")(ptr(p.t), ptr(out), p.S, p.T, p.ld, *args), what)
+    return p.out(out)
+
+
+def quotients(ts, lag: int):
+    """S/UnivariateTimeSeries.scala:45-53: ret(i) = ts(i + lag) / ts(i), T - lag values."""
+    return _resized("quotients", "sts_quotients", ts, lambda T: T - lag, lag, 0)
+
+
+def price2ret(ts, lag: int):
+    """S/UnivariateTimeSeries.scala:55-63: ret(i) = ts(i + lag) / ts(i) - 1.0, T - lag values."""
+    return _resized("price2ret", "sts_quotients", ts, lambda T: T - lag, lag, 1)
+
+
+def fillWithDefault(values, filler: float):
+    """S/UnivariateTimeSeries.scala:233-241: NaN -> filler."""
+    return _same_shape("fillWithDefault", "sts_fill_with_default", values, float(filler))
+
+
+def downsample(values, n: int, phase: int = 0):
+    """S/UnivariateTimeSeries.scala:308-321: every n-th value from `phase` on,
+    ceil((T - phase) / n) values."""
+    return _resized("downsample", "sts_downsample", values,
+                    lambda T: -(-(T - phase) // n) if n >= 1 and 0 <= phase < T else 0, n, phase)
+
+
+def upsample(values, n: int, phase: int = 0, useZero: bool = False):
+    """S/UnivariateTimeSeries.scala:331-345: T * n values, values(j) at phase + j * n and NaN
+    (or 0.0 with useZero) elsewhere.  phase outside [0, n) raises IllegalArgumentException (the
+    reference runs off its array there)."""
+    return _resized("upsample", "sts_upsample", values, lambda T: T * n if n >= 1 else 0, n, phase, int(bool(useZero)))
+
+
+def _first_last(ts, want_first: bool):
+    p = Panel(ts)
+    lib = _native.lib()
+    if p.device:
+        import torch
+        res = torch.empty((p.S,), dtype=torch.int64, device=p.t.device)
+        f, l = (ptr(res), None) if want_first else (None, ptr(res))
+        check(lib.sts_first_last_not_nan(ptr(p.t), p.S, p.T, p.ld, f, l, p.stream), "firstNotNaN / lastNotNaN")
+    else:
+        res = np.empty((p.S,), dtype=np.int64)
+        f, l = (ptr(res), None) if want_first else (None, ptr(res))
+        check(lib.sts_first_last_not_nan_host(ptr(p.t), p.S, p.T, p.ld, f, l), "firstNotNaN / lastNotNaN")
+    return int(res[0]) if p.squeeze else res
+
+
+def firstNotNaN(ts):
+    """S/UnivariateTimeSeries.scala:119-128: the first non-NaN position, T when there is none;
+    an int for a series, an (S,) int64 array for a panel."""
+    return _first_last(ts, True)
+
+
+def lastNotNaN(ts):
+    """S/UnivariateTimeSeries.scala:130-139: the last non-NaN position, -1 when there is none."""
+    return _first_last(ts, False)
+
+
+def _rows(ts, bounds):
+    """ts[a:b] for a series, [ts[s, a_s:b_s]] for a panel"""
+    if isinstance(bounds, tuple):
+        return ts[bounds[0]:bounds[1]]
+    return [ts[s][a:b] for s, (a, b) in enumerate(bounds)]
+
+
+def trimLeading(ts):
+    """S/UnivariateTimeSeries.scala:98-105: ts(firstNotNaN until length), empty when all NaN.  A
+    slice for a series, a list of per-series slices for a panel."""
+    first = firstNotNaN(ts)
+    T = int(ts.shape[-1])
+    if isinstance(first, int):
+        return _rows(ts, (first, T))
+    return _rows(ts, [(int(f), T) for f in first.tolist()])
+
+
+def trimTrailing(ts):
+    """S/UnivariateTimeSeries.scala:110-117, the reference's own bounds: ts(0 until lastNotNaN),
+    which drops the last valid value, and an empty series when lastNotNaN <= 0."""
+    last = lastNotNaN(ts)
+    if isinstance(last, int):
+        return _rows(ts, (0, max(last, 0)))
+    return _rows(ts, [(0, max(int(l), 0)) for l in last.tolist()])
+
+
+def differencesOfOrderD(ts, d: int):
+    """S/UnivariateTimeSeries.scala:438-450: d sweeps of differencesAtLag(_, _, 1, i), full length."""
+    return _same_shape("differencesOfOrderD", "sts_diff_order_d", ts, d)
+
+
+def inverseDifferencesOfOrderD(diffedTs, d: int):
+    """S/UnivariateTimeSeries.scala:459-465: the sweeps i = d..1 of inverseDifferencesAtLag(_, _, 1, i)."""
+    return _same_shape("inverseDifferencesOfOrderD", "sts_inverse_diff_order_d", diffedTs, d)

@@ -1,4 +1,5 @@
-"""Loader and ctypes bindings for libsts_hip.so (the C ABI in include/sts.h).
+"""Loader and ctypes bindings for libsts_hip.so (the C ABI in include/sts.h and
+include/sts_transforms.h).
 
 This is the Python analogue of the JNI shim: plain pointers and
 sizes cross the boundary, no torch types.  There is deliberately NO fallback:
@@ -120,6 +121,42 @@ SIGNATURES = {
                                   _c_vp]),
 }
 
+# The panel transforms of include/sts_transforms.h, a sibling header with the same contracts:
+# a table of its own, bound by load_library / load_variant together with SIGNATURES
+# (tests/test_transforms_cpu.py holds it to its header as tests/test_abi.py holds SIGNATURES to sts.h).
+_PANELS = [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64]     # in, out, S, T, ld_in, ld_out
+_PANELS_HOST = [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64]        # in, out, S, T, ld
+TRANSFORM_SIGNATURES = {
+    "sts_quotients": (_c_int, _PANELS + [_c_int, _c_int, _c_vp]),
+    "sts_fill_quotients": (_c_int, _PANELS + [_c_int, _c_int, _c_int, _c_vp, _c_vp]),
+    "sts_fill_with_default": (_c_int, _PANELS + [_c_dbl, _c_vp]),
+    "sts_downsample": (_c_int, _PANELS + [_c_int, _c_int, _c_vp]),
+    "sts_upsample": (_c_int, _PANELS + [_c_int, _c_int, _c_int, _c_vp]),
+    "sts_first_last_not_nan": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp]),
+    "sts_inverse_diff_at_lag": (_c_int, _PANELS + [_c_int, _c_int, _c_vp]),
+    "sts_diff_order_d": (_c_int, _PANELS + [_c_int, _c_vp]),
+    "sts_inverse_diff_order_d": (_c_int, _PANELS + [_c_int, _c_vp]),
+    "sts_quotients_host": (_c_int, _PANELS_HOST + [_c_int, _c_int]),
+    "sts_fill_quotients_host": (_c_int, _PANELS_HOST + [_c_int, _c_int, _c_int, _c_vp]),
+    "sts_fill_with_default_host": (_c_int, _PANELS_HOST + [_c_dbl]),
+    "sts_downsample_host": (_c_int, _PANELS_HOST + [_c_int, _c_int]),
+    "sts_upsample_host": (_c_int, _PANELS_HOST + [_c_int, _c_int, _c_int]),
+    "sts_first_last_not_nan_host": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp]),
+    "sts_inverse_diff_at_lag_host": (_c_int, _PANELS_HOST + [_c_int, _c_int]),
+    "sts_diff_order_d_host": (_c_int, _PANELS_HOST + [_c_int]),
+    "sts_inverse_diff_order_d_host": (_c_int, _PANELS_HOST + [_c_int]),
+}
+
+
+def _bind(handle):
+    for table in (SIGNATURES, TRANSFORM_SIGNATURES):
+        for name, (res, args) in table.items():
+            fn = getattr(handle, name)
+            fn.restype = res
+            fn.argtypes = args
+    return handle
+
+
 _lib = None
 _lock = threading.Lock()
 _inited = set()
@@ -138,12 +175,7 @@ def load_library(path: str = LIB_PATH):
                 raise NativeLibraryError(
                     "libsts_hip.so not found at %s: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
                     " (there is no CPU fallback)" % path)
-            lib = ctypes.CDLL(path)
-            for name, (res, args) in SIGNATURES.items():
-                fn = getattr(lib, name)
-                fn.restype = res
-                fn.argtypes = args
-            _lib = lib
+            _lib = _bind(ctypes.CDLL(path))
     return _lib
 
 
@@ -175,12 +207,7 @@ def load_variant(path: str):
         if path not in _variants:
             if not os.path.exists(path):
                 raise NativeLibraryError("library variant not found at %s" % path)
-            v = ctypes.CDLL(path)
-            for name, (res, args) in SIGNATURES.items():
-                fn = getattr(v, name)
-                fn.restype = res
-                fn.argtypes = args
-            _variants[path] = v
+            _variants[path] = _bind(ctypes.CDLL(path))
     return _variants[path]
 
 

@@ -11,6 +11,8 @@ reference's own documentation and configs use are provided as fused single-pass 
                             (README.md:61, BASELINE config C4) -> sts_ar_fit_remove
   fill_diff_ewma(m, lag, s) fill(m) -> differencesAtLag(lag) -> EWMAModel(s).add
                             (BASELINE config C2) -> sts_fill_diff_ewma
+  fill_returns(m, lag)      fill(m) -> price2ret(lag): the reference README's prices -> fill ->
+                            returnRates -> sts_fill_quotients
 """
 from __future__ import annotations
 
@@ -61,6 +63,36 @@ def fill_diff_ewma(method: str, lag: int, smoothing):
             check(lib.sts_fill_diff_ewma_host(ptr(p.t), ptr(out), p.S, p.T, p.ld, code, lag, ptr(sm), None),
                   "fill_diff_ewma")
         return p.out(out)
+    return op
+
+
+def fill_quotients(panel, method: str, lag: int = 1, minusOne: bool = True):
+    """fillts(method) then quotients(lag) (minusOne: price2ret(lag)) of a series or panel in one
+    call: (T - lag,) or (S, T - lag).  fill("previous") with 1 <= lag <= 32 is one pass over HBM."""
+    from .UnivariateTimeSeries import fill_method_code
+    code = fill_method_code(method)
+    p = Panel(panel)
+    w = max(p.T - lag, 0)
+    out = p.empty(T=w)
+    lib = _native.lib()
+    if p.device:
+        check(lib.sts_fill_quotients(ptr(p.t), ptr(out), p.S, p.T, p.ld, w, code, lag, int(bool(minusOne)), None,
+                                     p.stream), "fill_quotients")
+    else:
+        check(lib.sts_fill_quotients_host(ptr(p.t), ptr(out), p.S, p.T, p.ld, code, lag, int(bool(minusOne)), None),
+              "fill_quotients")
+    return p.out(out)
+
+
+def fill_returns(method: str, lag: int = 1):
+    """`series => price2ret(fillts(series, method), lag)` as one fused device call over the panel
+    (mapSeries needs the index of the result: rdd.index[lag:])."""
+    from .UnivariateTimeSeries import fill_method_code
+    fill_method_code(method)   # an unknown method raises here, as fillts would
+
+    @batched
+    def op(panel):
+        return fill_quotients(panel, method, lag, True)
     return op
 
 

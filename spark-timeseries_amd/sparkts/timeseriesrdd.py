@@ -45,6 +45,72 @@ class TimeSeriesRDD:
         """fill(method) == mapSeries(UnivariateTimeSeries.fillts(_, method))."""
         return self._derive(uts.fillts(self.data, method))
 
+    def _islice(self, n: int):
+        """index.islice(n, index.size); an index that cannot be sliced is dropped"""
+        if self.index is None:
+            return None
+        try:
+            return self.index[n:]
+        except (TypeError, IndexError, KeyError):
+            return None
+
+    def _sliced(self, data, n: int) -> "TimeSeriesRDD":
+        return TimeSeriesRDD(self._islice(n), self.keys, data, self.partitions)
+
+    def _select(self, keep) -> "TimeSeriesRDD":
+        """filter: the records with keep[s], their keys and partitions, in order"""
+        idx = [s for s, k in enumerate(keep) if k]
+        data = self.data[idx] if len(idx) != len(keep) else self.data
+        keys = [self.keys[s] for s in idx] if self.keys is not None else None
+        parts = [self.partitions[s] for s in idx] if self.partitions is not None else None
+        return TimeSeriesRDD(self.index, keys, data, parts)
+
+    # --- S/TimeSeriesRDD.scala:80-82 ---
+    def findSeries(self, key: str):
+        """filter(_._1 == key).first()._2: the first series recorded under `key`."""
+        if self.keys is None or key not in self.keys:
+            raise KeyError(key)
+        return self.data[self.keys.index(key)]
+
+    # --- S/TimeSeriesRDD.scala:88-90 ---
+    def differences(self, n: int) -> "TimeSeriesRDD":
+        """Breeze's recursive diff(vec, n): the order-n differences without their first n
+        instants, index.islice(n, size).  Bit-identical: diff(v, n) subtracts neighbours n times,
+        the subtractions differencesOfOrderD makes from position n on."""
+        if n < 0 or n > int(self.data.shape[-1]):
+            from .errors import IllegalArgumentException
+            raise IllegalArgumentException("differences: order %d outside [0, %d]" % (n, int(self.data.shape[-1])))
+        return self._sliced(uts.differencesOfOrderD(self.data, n)[..., n:], n)
+
+    # --- S/TimeSeriesRDD.scala:96-98 ---
+    def quotients(self, n: int) -> "TimeSeriesRDD":
+        return self._sliced(uts.quotients(self.data, n), n)
+
+    # --- S/TimeSeriesRDD.scala:104-106 ---
+    def returnRates(self) -> "TimeSeriesRDD":
+        """mapSeries(price2ret(_, 1), index.islice(1, size))."""
+        return self._sliced(uts.price2ret(self.data, 1), 1)
+
+    def fillAndReturnRates(self, method: str) -> "TimeSeriesRDD":
+        """fill(method).returnRates() in one call (sts_fill_quotients; fill("previous") is one
+        pass over HBM)."""
+        from .pipelines import fill_quotients
+        return self._sliced(fill_quotients(self.data, method, 1, True), 1)
+
+    # --- S/TimeSeriesRDD.scala:115-126, by location: DateTimeIndex.locAtDateTime is not mirrored ---
+    def filterStartingBefore(self, loc: int) -> "TimeSeriesRDD":
+        """Keep the series whose first observation is at or before location `loc`
+        (firstNotNaN <= loc); keys and partitions of the survivors are kept."""
+        first = uts.firstNotNaN(self.data)
+        first = [first] if isinstance(first, int) else first.tolist()
+        return self._select([f <= loc for f in first])
+
+    def filterEndingAfter(self, loc: int) -> "TimeSeriesRDD":
+        """Keep the series whose last observation is at or after location `loc` (lastNotNaN >= loc)."""
+        last = uts.lastNotNaN(self.data)
+        last = [last] if isinstance(last, int) else last.tolist()
+        return self._select([l >= loc for l in last])
+
     # --- S/TimeSeriesRDD.scala:188-199 ---
     def mapSeries(self, f: Callable, index=None) -> "TimeSeriesRDD":
         """Apply f to every series; keys (and their order) are unchanged.  A closure marked
