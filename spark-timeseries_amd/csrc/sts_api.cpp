@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -1772,6 +1773,92 @@ int sts_gen_ar_panel(double* out, double* c, double* phi, int64_t s0, int64_t S,
     if ((r = ensure_device())) return r;
     HIP_TRY(sts::launch_gen_ar(out, c, phi, s0, S, T, ld, seed, p, as_stream(stream)), "gen_ar_panel");
     return STS_OK;
+}
+
+// ---- samplers: include/sts_sample.h (sts_sample.hip) ----
+
+// the arguments every sampler shares
+static int sample_args(const double* out, int64_t s0, int64_t S, int64_t n, int64_t ld, int64_t t0, const char* name) {
+    int r;
+    if ((r = check_panel(out, S, n, ld, name))) return r;
+    if (s0 < 0 || t0 < 0)
+        return fail(STS_ERR_BAD_ARG, "%s: negative first series (s0=%lld) or stream position (t0=%lld)", name,
+                    (long long)s0, (long long)t0);
+    return STS_OK;
+}
+
+static sts::SampleArgs sample_call(double* out, int64_t s0, int64_t S, int64_t n, int64_t ld, int64_t t0,
+                                   uint64_t seed) {
+    sts::SampleArgs a{};
+    a.out = out; a.s0 = s0; a.S = S; a.n = n; a.ld = ld; a.t0 = t0; a.seed = seed;
+    return a;
+}
+
+int sts_sample_normal(double* out, int64_t s0, int64_t S, int64_t n, int64_t ld, int64_t t0, uint64_t seed,
+                      void* stream) {
+    int r;
+    if ((r = sample_args(out, s0, S, n, ld, t0, "sample_normal"))) return r;
+    if (S * n == 0) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    const sts::SampleArgs a = sample_call(out, s0, S, n, ld, t0, seed);
+    HIP_TRY(timed(st, [&] { return sts::launch_sample_normal(a, st); }), "sample_normal");
+    return STS_OK;
+}
+
+static int garch_sample(bool ar, double* out, int64_t s0, int64_t S, int64_t n, int64_t ld, const double* c,
+                        const double* phi, const double* omega, const double* alpha, const double* beta, int64_t t0,
+                        uint64_t seed, void* stream, const char* name) {
+    int r;
+    if ((r = sample_args(out, s0, S, n, ld, t0, name))) return r;
+    if (S > 0 && (!omega || !alpha || !beta || (ar && (!c || !phi))))
+        return fail(STS_ERR_BAD_ARG, "%s: null model parameters", name);
+    if (S * n == 0) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    sts::SampleArgs a = sample_call(out, s0, S, n, ld, t0, seed);
+    a.c = c; a.phi = phi; a.omega = omega; a.alpha = alpha; a.beta = beta;
+    HIP_TRY(timed(st, [&] { return sts::launch_garch_sample(ar, a, st); }), name);
+    return STS_OK;
+}
+
+int sts_garch_sample(double* out, int64_t s0, int64_t S, int64_t n, int64_t ld, const double* omega,
+                     const double* alpha, const double* beta, int64_t t0, uint64_t seed, void* stream) {
+    return garch_sample(false, out, s0, S, n, ld, nullptr, nullptr, omega, alpha, beta, t0, seed, stream,
+                        "GARCHModel.sample");
+}
+
+int sts_argarch_sample(double* out, int64_t s0, int64_t S, int64_t n, int64_t ld, const double* c, const double* phi,
+                       const double* omega, const double* alpha, const double* beta, int64_t t0, uint64_t seed,
+                       void* stream) {
+    return garch_sample(true, out, s0, S, n, ld, c, phi, omega, alpha, beta, t0, seed, stream, "ARGARCHModel.sample");
+}
+
+// sample = addTimeDependentEffects(vec, vec) of the draws: the add entry point validates its own
+// arguments first (validate-only, no device), then the draws and the in-place add share the stream
+static int sample_then_add(double* out, int64_t s0, int64_t S, int64_t n, int64_t ld, int64_t t0, uint64_t seed,
+                           void* stream, const char* name, const std::function<int()>& add) {
+    int r;
+    if ((r = sample_args(out, s0, S, n, ld, t0, name))) return r;
+    if (!out) return STS_OK;   // an empty panel may come without a buffer (sts_arima_add insists on a dest)
+    bool has_work = false;
+    if ((r = sts::validate([&] { return add(); }, &has_work))) return r;
+    if (!has_work) return STS_OK;
+    if ((r = sts_sample_normal(out, s0, S, n, ld, t0, seed, stream))) return r;
+    return add();
+}
+
+int sts_ar_sample(double* out, int64_t s0, int64_t S, int64_t n, int64_t ld, const double* c, const double* coef,
+                  int p, int64_t t0, uint64_t seed, void* stream) {
+    return sample_then_add(out, s0, S, n, ld, t0, seed, stream, "ARModel.sample",
+                           [&] { return sts_ar_add(out, out, S, n, ld, ld, c, coef, p, stream); });
+}
+
+int sts_arima_sample(double* out, int64_t s0, int64_t S, int64_t n, int64_t ld, int p, int d, int q,
+                     int include_intercept, const double* coef, int64_t t0, uint64_t seed, void* stream) {
+    return sample_then_add(out, s0, S, n, ld, t0, seed, stream, "ARIMAModel.sample", [&] {
+        return sts_arima_add(out, out, S, n, ld, ld, p, d, q, include_intercept, coef, stream);
+    });
 }
 
 }  // extern "C"

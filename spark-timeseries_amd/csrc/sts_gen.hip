@@ -6,34 +6,12 @@
 //   AR(p) panels: phi = base * (1 + 0.1*(u_s - 0.5)), c = 1, innovations u_{s,t} - 0.5,
 //   built with ARModel.addTimeDependentEffects (S/models/Autoregression.scala:75-88).
 #include "sts_internal.hpp"
+#include "sts_normal.hpp"   // philox4x32_10, shared with the samplers
 
 #include <hip/hip_runtime.h>
 
 namespace sts {
 namespace {
-
-__device__ __forceinline__ void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                       uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0;
-        const uint32_t n2 = hi0 ^ c3 ^ k1;
-        c0 = n0;
-        c1 = lo1;
-        c2 = n2;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0;
-    out[1] = c1;
-    out[2] = c2;
-    out[3] = c3;
-}
 
 __device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
     const uint64_t m = ((uint64_t)(a >> 5) << 26) | (uint64_t)(b >> 6);
@@ -41,8 +19,8 @@ __device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
 }
 
 __device__ __forceinline__ void words(uint64_t seed, int64_t s, uint64_t t, uint32_t w[4]) {
-    philox((uint32_t)t, (uint32_t)(t >> 32), (uint32_t)(uint64_t)s, (uint32_t)((uint64_t)s >> 32),
-           (uint32_t)seed, (uint32_t)(seed >> 32), w);
+    philox4x32_10((uint32_t)t, (uint32_t)(t >> 32), (uint32_t)(uint64_t)s, (uint32_t)((uint64_t)s >> 32),
+                  (uint32_t)seed, (uint32_t)(seed >> 32), w);
 }
 
 __device__ __forceinline__ double series_u(uint64_t seed, int64_t s) {

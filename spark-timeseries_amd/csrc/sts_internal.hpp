@@ -8,6 +8,7 @@
 
 #include "sts.h"
 #include "sts_transforms.h"
+#include "sts_sample.h"
 
 namespace sts {
 
@@ -358,5 +359,16 @@ hipError_t launch_gen_panel(double* out, int64_t s0, int64_t S, int64_t T, int64
                             uint64_t seed, uint32_t nan_thr, hipStream_t st);
 hipError_t launch_gen_ar(double* out, double* c, double* phi, int64_t s0, int64_t S, int64_t T,
                          int64_t ld, uint64_t seed, int p, hipStream_t st);
+
+// samplers (sts_sample.hip; include/sts_sample.h): series s of the call draws
+// z(seed, s0 + s, t0 + i), i < n (sts_normal.hpp)
+struct SampleArgs {
+    double* out;          // S x n, ld
+    int64_t s0, S, n, ld, t0;
+    uint64_t seed;
+    const double *c, *phi, *omega, *alpha, *beta;   // per series (GARCH: omega, alpha, beta; ARGARCH: all)
+};
+hipError_t launch_sample_normal(const SampleArgs& a, hipStream_t st);
+hipError_t launch_garch_sample(bool ar, const SampleArgs& a, hipStream_t st);
 
 }  // namespace sts

@@ -1,5 +1,5 @@
-"""Loader and ctypes bindings for libsts_hip.so (the C ABI in include/sts.h and
-include/sts_transforms.h).
+"""Loader and ctypes bindings for libsts_hip.so (the C ABI in include/sts.h, include/sts_transforms.h
+and include/sts_sample.h).
 
 This is the Python analogue of the JNI shim: plain pointers and
 sizes cross the boundary, no torch types.  There is deliberately NO fallback:
@@ -147,9 +147,22 @@ TRANSFORM_SIGNATURES = {
     "sts_inverse_diff_order_d_host": (_c_int, _PANELS_HOST + [_c_int]),
 }
 
+# The samplers of include/sts_sample.h, the third sibling header (tests/test_sample_cpu.py holds this
+# table to it): out, s0, S, n, ld, then the model, then t0, seed, stream.
+_c_u64 = ctypes.c_uint64
+_DRAWS = [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64]             # out, s0, S, n, ld
+_STREAM_POS = [_c_i64, _c_u64, _c_vp]                        # t0, seed, stream
+SAMPLE_SIGNATURES = {
+    "sts_sample_normal": (_c_int, _DRAWS + _STREAM_POS),
+    "sts_garch_sample": (_c_int, _DRAWS + [_c_vp] * 3 + _STREAM_POS),
+    "sts_argarch_sample": (_c_int, _DRAWS + [_c_vp] * 5 + _STREAM_POS),
+    "sts_ar_sample": (_c_int, _DRAWS + [_c_vp, _c_vp, _c_int] + _STREAM_POS),
+    "sts_arima_sample": (_c_int, _DRAWS + [_c_int, _c_int, _c_int, _c_int, _c_vp] + _STREAM_POS),
+}
+
 
 def _bind(handle):
-    for table in (SIGNATURES, TRANSFORM_SIGNATURES):
+    for table in (SIGNATURES, TRANSFORM_SIGNATURES, SAMPLE_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(handle, name)
             fn.restype = res

@@ -16,15 +16,19 @@ ARIMAModel carries the whole TimeSeriesModel interface on device panels: remove 
 isStationary / isInvertible (:617-656).  `coefficients` is one vector (intercept, AR, MA) for
 one series or for every series of a panel, or (S, n) with one row per series.
 
-Not supported: method="css-bobyqa" (commons-math3's BOBYQAOptimizer is not restated), and
-sample(n, rand), which draws from a JVM RandomGenerator -- addTimeDependentEffects on the
-caller's own noise is the same computation.
+sample(n, rand, paths=None) (:517-520) is addTimeDependentEffects(vec, vec) of n draws made on
+the device from a sparkts.random.PhiloxGenerator (sts_arima_sample).
+
+Not supported: method="css-bobyqa" (commons-math3's BOBYQAOptimizer is not restated).
 """
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 
 from .. import _native
+from .. import random as _random
 from .._panel import Panel, check, is_torch, ptr
 from ..errors import IllegalArgumentException, NullPointerException, UnsupportedOperationException
 from .TimeSeriesModel import TimeSeriesModel
@@ -97,6 +101,19 @@ class ARIMAModel(TimeSeriesModel):
     def addTimeDependentEffects(self, ts, dest=None):
         """S/models/ARIMA.scala:498-510 (bit-exact); dest may be ts."""
         return self._effects(True, ts, dest)
+
+    def sample(self, n: int, rand, paths=None, device=None):
+        """S/models/ARIMA.scala:517-520 (bit-exact given the draws): (n,) for one coefficient
+        vector, (paths, n) for `paths` paths of it, (S, n) for (S, ncoef) coefficients."""
+        what = "ARIMAModel.sample"
+        _random.require_generator(rand, what)
+        ncoef = self._n(what)
+        lib = _native.lib()
+        return _random.run_sample(
+            what, n, rand, paths, [(self.coefficients, "coefficients", 1, ncoef)], device,
+            lambda out, S, v, t0, st: lib.sts_arima_sample(ptr(out), rand.first_series, S, n, n, self.p, self.d, self.q,
+                                                           int(bool(self.hasIntercept)), ptr(v[0]), t0,
+                                                           ctypes.c_uint64(rand.seed), st))
 
     def forecast(self, ts, nFuture: int):
         """S/models/ARIMA.scala:537-605: the fitted one-step values of ts followed by nFuture

@@ -7,9 +7,12 @@ returned ARModel holds c / coefficients per series (scalars for a single series)
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 
 from .. import _native
+from .. import random as _random
 from .._panel import Panel, check, is_torch, ptr
 from .TimeSeriesModel import TimeSeriesModel
 
@@ -65,6 +68,19 @@ class ARModel(TimeSeriesModel):
     def addTimeDependentEffects(self, ts, destTs=None):
         """S/models/Autoregression.scala:75-88 (IIR, bit-exact)."""
         return self._run(True, ts, destTs)
+
+    def sample(self, n: int, rand, paths=None, device=None):
+        """S/models/Autoregression.scala:90-93: addTimeDependentEffects(vec, vec) of n draws of
+        rand (a sparkts.random.PhiloxGenerator), on the device.  (n,) for one model, (paths, n)
+        for `paths` paths of it, (S, n) for per-series c / coefficients."""
+        _random.require_generator(rand, "ARModel.sample")
+        lib = _native.lib()
+        shp = _random._shape(self.coefficients)
+        coef, order = (self.coefficients, int(shp[-1])) if shp else ([self.coefficients], 1)   # a bare float: AR(1)
+        return _random.run_sample(
+            "ARModel.sample", n, rand, paths, [(self.c, "c", 0, None), (coef, "coefficients", 1, order)], device,
+            lambda out, S, v, t0, st: lib.sts_ar_sample(ptr(out), rand.first_series, S, n, n, ptr(v[0]), ptr(v[1]),
+                                                        order, t0, ctypes.c_uint64(rand.seed), st))
 
 
 class Autoregression:

@@ -11,10 +11,17 @@ residuals on the device, then GARCH.fitModel of the residuals.
 Note GARCHModel.gradient (:94-114) returns its components in the order (alpha, beta,
 omega) while the optimizer's point is (omega, alpha, beta); that is the reference's code
 and it is reproduced, since it decides the optimizer's path.
+
+sample(n, rand, paths=None) (:162-183, :235-256) runs sampleWithVariances as one fused kernel
+(sts_garch_sample / sts_argarch_sample): rand is a sparkts.random.PhiloxGenerator, the draws are
+made on the device and only the paths are written.
 """
 from __future__ import annotations
 
+import ctypes
+
 from .. import _native
+from .. import random as _random
 from .._panel import Panel, check, ptr
 from ..errors import NullPointerException
 from .TimeSeriesModel import TimeSeriesModel
@@ -61,6 +68,18 @@ class GARCHModel(TimeSeriesModel):
     def addTimeDependentEffects(self, ts, dest=None):
         """S/models/GARCH.scala:144-159 (bit-exact); dest may be ts."""
         return self._effects(True, ts, dest)
+
+    def sample(self, n: int, rand, paths=None, device=None):
+        """S/models/GARCH.scala:162-183 (bit-exact given the draws): (n,) for scalar parameters,
+        (paths, n) for `paths` paths of them (path j on stream rand.first_series + j), (S, n) for
+        per-series parameters.  The first element is 0.0, as in the reference."""
+        _random.require_generator(rand, "GARCHModel.sample")
+        lib = _native.lib()
+        return _random.run_sample(
+            "GARCHModel.sample", n, rand, paths,
+            [(self.omega, "omega", 0, None), (self.alpha, "alpha", 0, None), (self.beta, "beta", 0, None)], device,
+            lambda out, S, v, t0, st: lib.sts_garch_sample(ptr(out), rand.first_series, S, n, n, ptr(v[0]), ptr(v[1]),
+                                                           ptr(v[2]), t0, ctypes.c_uint64(rand.seed), st))
 
     def _loglik_grad(self, ts):
         import torch
@@ -111,6 +130,17 @@ class ARGARCHModel(TimeSeriesModel):
     def addTimeDependentEffects(self, ts, dest=None):
         """S/models/GARCH.scala:219-234 (bit-exact)."""
         return self._effects(True, ts, dest)
+
+    def sample(self, n: int, rand, paths=None, device=None):
+        """S/models/GARCH.scala:235-256 (bit-exact given the draws); shapes as GARCHModel.sample."""
+        _random.require_generator(rand, "ARGARCHModel.sample")
+        lib = _native.lib()
+        return _random.run_sample(
+            "ARGARCHModel.sample", n, rand, paths,
+            [(v, k, 0, None) for v, k in ((self.c, "c"), (self.phi, "phi"), (self.omega, "omega"),
+                                          (self.alpha, "alpha"), (self.beta, "beta"))], device,
+            lambda out, S, v, t0, st: lib.sts_argarch_sample(ptr(out), rand.first_series, S, n, n, *[ptr(x) for x in v],
+                                                             t0, ctypes.c_uint64(rand.seed), st))
 
 
 class GARCH:
