@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "sts_internal.hpp"
+#include "sts_index.hpp"
 
 namespace {
 
@@ -1859,6 +1860,93 @@ int sts_arima_sample(double* out, int64_t s0, int64_t S, int64_t n, int64_t ld, 
     return sample_then_add(out, s0, S, n, ld, t0, seed, stream, "ARIMAModel.sample", [&] {
         return sts_arima_add(out, out, S, n, ld, ld, p, d, q, include_intercept, coef, stream);
     });
+}
+
+// ---- date-time indices and rebasing: include/sts_index.h (sts_index.hip, sts_index.hpp) ----
+
+// the index every lookup shares: a validated uniform index in *u, or the irregular form's checks
+static int index_args(int kind, int64_t start_ms, int64_t periods, int step, const int64_t* instants,
+                      int64_t n_instants, sts::ix::Uniform* u, const char* name) {
+    if (kind == STS_INDEX_IRREGULAR) {
+        if (n_instants < 0) return fail(STS_ERR_BAD_ARG, "%s: negative index size %lld", name, (long long)n_instants);
+        if (n_instants > 0 && !instants) return fail(STS_ERR_BAD_ARG, "%s: null instants", name);
+        return STS_OK;
+    }
+    const char* why = sts::ix::make_uniform(kind, start_ms, periods, step, u);
+    if (why)
+        return fail(STS_ERR_BAD_ARG, "%s: %s (kind=%d, start=%lld, periods=%lld, step=%d)", name, why, kind,
+                    (long long)start_ms, (long long)periods, step);
+    return STS_OK;
+}
+
+int sts_index_instants(int kind, int64_t start_ms, int64_t periods, int step, const int64_t* instants,
+                       int64_t n_instants, int64_t* out, void* stream) {
+    int r;
+    sts::ix::Uniform u{};
+    if ((r = index_args(kind, start_ms, periods, step, instants, n_instants, &u, "toMillisArray"))) return r;
+    const int64_t n = kind == STS_INDEX_IRREGULAR ? n_instants : periods;
+    if (n == 0) return STS_OK;
+    if (!out) return fail(STS_ERR_BAD_ARG, "toMillisArray: null output");
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    if (kind == STS_INDEX_IRREGULAR)
+        HIP_TRY(hipMemcpyAsync(out, instants, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, st), "toMillisArray");
+    else
+        HIP_TRY(sts::launch_index_instants(u, out, st), "toMillisArray");
+    return STS_OK;
+}
+
+int sts_index_locs(const int64_t* millis, int64_t n, int kind, int64_t start_ms, int64_t periods, int step,
+                   const int64_t* instants, int64_t n_instants, int64_t* loc, void* stream) {
+    int r;
+    sts::ix::Uniform u{};
+    if (n < 0) return fail(STS_ERR_BAD_ARG, "locAtDateTime: negative count %lld", (long long)n);
+    if ((r = index_args(kind, start_ms, periods, step, instants, n_instants, &u, "locAtDateTime"))) return r;
+    if (n == 0) return STS_OK;
+    if (!millis || !loc) return fail(STS_ERR_BAD_ARG, "locAtDateTime: null timestamps or output");
+    if ((r = ensure_device())) return r;
+    HIP_TRY(sts::launch_index_locs(millis, n, kind == STS_INDEX_IRREGULAR ? nullptr : &u, instants, n_instants, loc,
+                                   as_stream(stream)), "locAtDateTime");
+    return STS_OK;
+}
+
+int sts_rebase_shift(const double* in, double* out, int64_t S, int64_t T_in, int64_t T_out, int64_t ld_in,
+                     int64_t ld_out, int64_t start_loc, double default_value, void* stream) {
+    int r;
+    if ((r = check_panel(in, S, T_in, ld_in, "rebase"))) return r;
+    if ((r = check_panel(out, S, T_out, ld_out, "rebase"))) return r;
+    if (S * T_out == 0) return STS_OK;
+    if (in == out) return fail(STS_ERR_BAD_ARG, "rebase: out must not alias in");
+    if ((r = ensure_device())) return r;
+    HIP_TRY(sts::launch_rebase_shift(in, out, S, T_in, T_out, ld_in, ld_out, start_loc, default_value,
+                                     as_stream(stream)), "rebase");
+    return STS_OK;
+}
+
+int sts_rebase_map(const double* in, double* out, int64_t S, int64_t T_in, int64_t T_out, int64_t ld_in,
+                   int64_t ld_out, const int64_t* map, double default_value, void* stream) {
+    int r;
+    if ((r = check_panel(in, S, T_in, ld_in, "rebase"))) return r;
+    if ((r = check_panel(out, S, T_out, ld_out, "rebase"))) return r;
+    if (S * T_out == 0) return STS_OK;
+    if (!map) return fail(STS_ERR_BAD_ARG, "rebase: null map");
+    if (in == out) return fail(STS_ERR_BAD_ARG, "rebase: out must not alias in");
+    if ((r = ensure_device())) return r;
+    HIP_TRY(sts::launch_rebase_map(in, out, S, T_in, T_out, ld_in, ld_out, map, default_value, as_stream(stream)),
+            "rebase");
+    return STS_OK;
+}
+
+int sts_align_uniform(const double* values, const int64_t* offsets, const int64_t* start_loc, int64_t S,
+                      int64_t T_out, double* out, int64_t ld_out, double default_value, void* stream) {
+    int r;
+    if ((r = check_panel(out, S, T_out, ld_out, "timeSeriesRDD"))) return r;
+    if (S * T_out == 0) return STS_OK;
+    if (!offsets || !start_loc) return fail(STS_ERR_BAD_ARG, "timeSeriesRDD: null offsets or start locations");
+    if ((r = ensure_device())) return r;
+    HIP_TRY(sts::launch_align_uniform(values, offsets, start_loc, S, T_out, out, ld_out, default_value,
+                                      as_stream(stream)), "timeSeriesRDD");
+    return STS_OK;
 }
 
 }  // extern "C"

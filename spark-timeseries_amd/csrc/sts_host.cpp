@@ -773,4 +773,39 @@ int sts_inverse_diff_order_d_host(const double* in, double* out, int64_t S, int6
     });
 }
 
+// ---- rebasing (include/sts_index.h i3, i4): the output is packed, T_out wide (0 for a shape the
+// entry point rejects, as above) ----
+
+int sts_rebase_shift_host(const double* in, double* out, int64_t S, int64_t T_in, int64_t T_out, int64_t ld,
+                          int64_t start_loc, double default_value) {
+    const int64_t w = (T_out >= 0 && T_out <= 0x7fffffffLL) ? T_out : 0;
+    return staged(S, T_in, ld, {in_panel(in), out_vec(out, w)}, [&](const Call& c) {
+        return sts_rebase_shift(c.in(0), c.out(1), c.n, T_in, T_out, c.ld, T_out, start_loc, default_value, c.st);
+    });
+}
+
+// the map is shared by every series: it is uploaded once, outside the pipeline (as bgbp_host's shared
+// factors are), after the entry point has accepted the call on the caller's pointers
+int sts_rebase_map_host(const double* in, double* out, int64_t S, int64_t T_in, int64_t T_out, int64_t ld,
+                        const int64_t* map, double default_value) {
+    bool work = false;
+    const int r = sts::validate(
+        [&] { return sts_rebase_map(in, out, S, T_in, T_out, ld, T_out, map, default_value, nullptr); }, &work);
+    if (r || !work) return r;
+    void* dm = nullptr;
+    hipError_t e = hipMalloc(&dm, (size_t)T_out * sizeof(int64_t));
+    if (e != hipSuccess) return hip_status(e, "hipMalloc(map)");
+    e = hipMemcpy(dm, map, (size_t)T_out * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(dm);
+        return hip_status(e, "hipMemcpy(map)");
+    }
+    const int st = staged(S, T_in, ld, {in_panel(in), out_vec(out, T_out)}, [&](const Call& c) {
+        return sts_rebase_map(c.in(0), c.out(1), c.n, T_in, T_out, c.ld, T_out, c.st ? static_cast<const int64_t*>(dm) : map,
+                              default_value, c.st);
+    });
+    (void)hipFree(dm);   // every chunk is back
+    return st;
+}
+
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include "sts.h"
 #include "sts_transforms.h"
 #include "sts_sample.h"
+#include "sts_index.h"
 
 namespace sts {
 
@@ -370,5 +371,18 @@ struct SampleArgs {
 };
 hipError_t launch_sample_normal(const SampleArgs& a, hipStream_t st);
 hipError_t launch_garch_sample(bool ar, const SampleArgs& a, hipStream_t st);
+
+// date-time indices and rebasing (sts_index.hip; include/sts_index.h i1-i5).  A uniform index
+// arrives validated (sts_index.hpp make_uniform); u == nullptr in launch_index_locs: irregular
+namespace ix { struct Uniform; }
+hipError_t launch_index_instants(const ix::Uniform& u, int64_t* out, hipStream_t st);
+hipError_t launch_index_locs(const int64_t* millis, int64_t n, const ix::Uniform* u, const int64_t* instants,
+                             int64_t n_instants, int64_t* loc, hipStream_t st);
+hipError_t launch_rebase_shift(const double* in, double* out, int64_t S, int64_t T_in, int64_t T_out, int64_t ld_in,
+                               int64_t ld_out, int64_t shift, double dflt, hipStream_t st);
+hipError_t launch_rebase_map(const double* in, double* out, int64_t S, int64_t T_in, int64_t T_out, int64_t ld_in,
+                             int64_t ld_out, const int64_t* map, double dflt, hipStream_t st);
+hipError_t launch_align_uniform(const double* values, const int64_t* offsets, const int64_t* start_loc, int64_t S,
+                                int64_t T_out, double* out, int64_t ld_out, double dflt, hipStream_t st);
 
 }  // namespace sts

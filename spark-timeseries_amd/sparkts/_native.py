@@ -1,5 +1,5 @@
-"""Loader and ctypes bindings for libsts_hip.so (the C ABI in include/sts.h, include/sts_transforms.h
-and include/sts_sample.h).
+"""Loader and ctypes bindings for libsts_hip.so (the C ABI in include/sts.h, include/sts_transforms.h,
+include/sts_sample.h and include/sts_index.h).
 
 This is the Python analogue of the JNI shim: plain pointers and
 sizes cross the boundary, no torch types.  There is deliberately NO fallback:
@@ -160,9 +160,25 @@ SAMPLE_SIGNATURES = {
     "sts_arima_sample": (_c_int, _DRAWS + [_c_int, _c_int, _c_int, _c_int, _c_vp] + _STREAM_POS),
 }
 
+# Date-time indices and rebasing, include/sts_index.h, the fourth sibling header (tests/test_index_cpu.py
+# holds this table to it).  An index travels as kind, start_ms, periods, step, instants, n_instants.
+_INDEX = [_c_int, _c_i64, _c_i64, _c_int, _c_vp, _c_i64]
+_REBASE = [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64]     # in, out, S, T_in, T_out, ld_in, ld_out
+_REBASE_HOST = [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64]        # in, out, S, T_in, T_out, ld
+INDEX_SIGNATURES = {
+    "sts_index_instants": (_c_int, _INDEX + [_c_vp, _c_vp]),
+    "sts_index_locs": (_c_int, [_c_vp, _c_i64] + _INDEX + [_c_vp, _c_vp]),
+    "sts_rebase_shift": (_c_int, _REBASE + [_c_i64, _c_dbl, _c_vp]),
+    "sts_rebase_map": (_c_int, _REBASE + [_c_vp, _c_dbl, _c_vp]),
+    "sts_align_uniform": (_c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_dbl, _c_vp]),
+    "sts_rebase_shift_host": (_c_int, _REBASE_HOST + [_c_i64, _c_dbl]),
+    "sts_rebase_map_host": (_c_int, _REBASE_HOST + [_c_vp, _c_dbl]),
+}
+INDEX_DAYS, INDEX_HOURS, INDEX_BUSINESS_DAYS, INDEX_IRREGULAR = 0, 1, 2, 3
+
 
 def _bind(handle):
-    for table in (SIGNATURES, TRANSFORM_SIGNATURES, SAMPLE_SIGNATURES):
+    for table in (SIGNATURES, TRANSFORM_SIGNATURES, SAMPLE_SIGNATURES, INDEX_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(handle, name)
             fn.restype = res

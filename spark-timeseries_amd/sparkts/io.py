@@ -135,7 +135,8 @@ def observation_key_order(keys, num_partitions: int = 1):
 
 
 def timeSeriesRDDFromObservations(targetIndex, keys, timestamps, values, device=None, numPartitions=1):
-    """S/TimeSeriesRDD.scala:493-542.  targetIndex: sorted instants (int64 / datetime64);
+    """S/TimeSeriesRDD.scala:493-542.  targetIndex: sorted instants (int64 / datetime64), looked up on
+    the host, or a DateTimeIndex (sparkts.datetimeindex), looked up on the device (timestamps in ms);
     keys: one string per observation; timestamps: one instant per observation; numPartitions:
     the input RDD's partition count (the reference shuffles into that many partitions).
     Series come out in the reference's record order: by hash partition of the key, then by
@@ -147,6 +148,9 @@ def timeSeriesRDDFromObservations(targetIndex, keys, timestamps, values, device=
     dev = _device(device)
     if numPartitions < 1:
         raise ValueError("numPartitions must be >= 1")
+    from .datetimeindex import DateTimeIndex
+    if isinstance(targetIndex, DateTimeIndex):
+        return _from_observations_indexed(targetIndex, keys, timestamps, values, dev, numPartitions)
     idx = np.asarray(targetIndex)
     ts = np.asarray(timestamps)
     if idx.dtype.kind == "M":
@@ -174,6 +178,30 @@ def timeSeriesRDDFromObservations(targetIndex, keys, timestamps, values, device=
     return rdd
 
 
+def _from_observations_indexed(targetIndex, keys, timestamps, values, dev, numPartitions):
+    """timeSeriesRDDFromObservations with a DateTimeIndex: the timestamps (ms) go to the device and
+    locAtDateTime runs there (sts_index_locs); the scatter is the same call as above.  A negative
+    loc (absent; an irregular index answers -(insertion point) - 1) drops the observation."""
+    from .datetimeindex import _millis_array
+    from .timeseriesrdd import TimeSeriesRDD
+    torch = _torch()
+    ts = np.asarray(timestamps)
+    ts = _millis_array(ts if ts.dtype.kind in "Miu" else list(timestamps))
+    key_list = [str(k) for k in keys]
+    order, parts = observation_key_order(key_list, numPartitions)
+    rank = {k: i for i, k in enumerate(order)}
+    sid = np.fromiter((rank[k] for k in key_list), dtype=np.int32, count=len(key_list))
+    S, T, n = len(order), len(targetIndex), len(ts)
+    panel = torch.empty((S, T), dtype=torch.float64, device=dev)
+    sid_d = torch.as_tensor(sid, device=dev)
+    val_d = torch.as_tensor(np.asarray(values, dtype=np.float64), device=dev)
+    with torch.cuda.device(dev):
+        loc_d = targetIndex.locsAtDateTimes(torch.as_tensor(ts, device=dev))
+    check(_native.lib().sts_observations_to_panel(ptr(sid_d), ptr(loc_d), ptr(val_d), n, ptr(panel), S, T, T,
+                                                  _stream(dev)), "timeSeriesRDDFromObservations")
+    return TimeSeriesRDD(targetIndex, list(order), panel, partitions=parts)
+
+
 def csv_parse(text: bytes):
     """`key,v1,...,vn` lines -> (keys, (S, T) float64 host array)."""
     buf = np.frombuffer(text, dtype=np.uint8)
@@ -194,9 +222,10 @@ def csv_parse(text: bytes):
     return keys, vals
 
 
-def timeSeriesRDDFromCsv(path: str, device=None):
+def timeSeriesRDDFromCsv(path: str, device=None, parseIndex=False):
     """S/TimeSeriesRDD.scala:547-561: every part file of `path` (lines `key,v1,...`) plus the
-    `timeIndex` file (kept as its string; DateTimeIndex parsing is out of scope)."""
+    `timeIndex` file: kept as its string by default, parsed with datetimeindex.fromString (as the
+    reference does) when parseIndex is true."""
     from .timeseriesrdd import TimeSeriesRDD
     torch = _torch()
     dev = _device(device)
@@ -207,6 +236,9 @@ def timeSeriesRDDFromCsv(path: str, device=None):
     ti = os.path.join(path, "timeIndex")
     if os.path.exists(ti):
         index = open(ti).readline().rstrip("\n")
+        if parseIndex:
+            from .datetimeindex import fromString
+            index = fromString(index)
     panel = torch.as_tensor(vals, device=dev)
     return TimeSeriesRDD(index, keys, panel)
 

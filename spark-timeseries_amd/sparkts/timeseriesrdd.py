@@ -2,8 +2,11 @@
 
 A TimeSeriesRDD here is one PARTITION of keyed series resident in HBM: the (S, T)
 panel of this rank's records (series-contiguous, exactly each record's
-DenseVector.data), their keys, and the shared time index (metadata only -- the
-hot path is position based).  Partitioning follows Spark's
+DenseVector.data), their keys, and the shared time index.  The hot path is position
+based and takes any index as metadata; with a DateTimeIndex
+(sparkts.datetimeindex) the panel can also be sliced by date, rebased onto another index
+(withIndex) and built from series with indices of their own (timeSeriesRDD), on the
+device (include/sts_index.h).  Partitioning follows Spark's
 `parallelize` slicing (contiguous key ranges per partition, `shard_range`); one
 process per GPU owns one partition.  fill / mapSeries are narrow maps: no data
 crosses ranks.  The only collective is `all_gather_results`, an all-gather (RCCL
@@ -97,19 +100,90 @@ class TimeSeriesRDD:
         from .pipelines import fill_quotients
         return self._sliced(fill_quotients(self.data, method, 1, True), 1)
 
-    # --- S/TimeSeriesRDD.scala:115-126, by location: DateTimeIndex.locAtDateTime is not mirrored ---
-    def filterStartingBefore(self, loc: int) -> "TimeSeriesRDD":
+    # --- S/TimeSeriesRDD.scala:115-126 ---
+    def _loc(self, dt):
+        """an int is a location as it is; a date-time goes through index.locAtDateTime"""
+        import numbers
+        if isinstance(dt, numbers.Integral) and not isinstance(dt, bool):
+            return int(dt)
+        if not _is_datetime_index(self.index):
+            raise TypeError("a date-time argument needs a DateTimeIndex (sparkts.datetimeindex), not %s"
+                            % type(self.index).__name__)
+        return self.index.locAtDateTime(dt)
+
+    def filterStartingBefore(self, loc) -> "TimeSeriesRDD":
         """Keep the series whose first observation is at or before location `loc`
-        (firstNotNaN <= loc); keys and partitions of the survivors are kept."""
+        (firstNotNaN <= loc); keys and partitions of the survivors are kept.  A date-time `loc` is
+        index.locAtDateTime(loc), as in the reference."""
+        loc = self._loc(loc)
         first = uts.firstNotNaN(self.data)
         first = [first] if isinstance(first, int) else first.tolist()
         return self._select([f <= loc for f in first])
 
-    def filterEndingAfter(self, loc: int) -> "TimeSeriesRDD":
-        """Keep the series whose last observation is at or after location `loc` (lastNotNaN >= loc)."""
+    def filterEndingAfter(self, loc) -> "TimeSeriesRDD":
+        """Keep the series whose last observation is at or after location `loc` (lastNotNaN >= loc);
+        a date-time `loc` is index.locAtDateTime(loc)."""
+        loc = self._loc(loc)
         last = uts.lastNotNaN(self.data)
         last = [last] if isinstance(last, int) else last.tolist()
         return self._select([l >= loc for l in last])
+
+    # --- S/TimeSeriesRDD.scala:159-172, S/TimeSeriesUtils.scala:65-203 ---
+    def withIndex(self, newIndex, defaultValue: float = float("nan")) -> "TimeSeriesRDD":
+        """Rebase every series onto `newIndex`: out(s, j) is the value at the first location of
+        newIndex's instant j in this index, `defaultValue` where it is absent (include/sts_index.h,
+        "Rebase").  Two uniform indices are a shift (sts_rebase_shift); every other pair is a lookup
+        made on the device (sts_index_locs) and a gather (sts_rebase_map)."""
+        from . import datetimeindex as dti
+        if not _is_datetime_index(self.index) or not _is_datetime_index(newIndex):
+            raise TypeError("withIndex needs DateTimeIndex objects (sparkts.datetimeindex) on both sides")
+        p = Panel(self.data)
+        lib = _native.lib()
+        n = len(newIndex)
+        out = p.empty(T=n)
+        dflt = float(defaultValue)
+        if isinstance(self.index, dti.UniformDateTimeIndex) and isinstance(newIndex, dti.UniformDateTimeIndex):
+            start = dti.uniform_start_loc(self.index, newIndex)
+            if p.device:
+                check(lib.sts_rebase_shift(ptr(p.t), ptr(out), p.S, p.T, n, p.ld, n, start, dflt, p.stream), "rebase")
+            else:
+                check(lib.sts_rebase_shift_host(ptr(p.t), ptr(out), p.S, p.T, n, p.ld, start, dflt), "rebase")
+        elif p.device:
+            m = self.index.locsAtDateTimes(_device_instants(newIndex, p.t.device, p.stream))
+            check(lib.sts_rebase_map(ptr(p.t), ptr(out), p.S, p.T, n, p.ld, n, ptr(m), dflt, p.stream), "rebase")
+        else:
+            import numpy as np
+            m = np.ascontiguousarray(self.index.locsAtDateTimes(newIndex.toMillisArray()), dtype=np.int64)
+            check(lib.sts_rebase_map_host(ptr(p.t), ptr(out), p.S, p.T, n, p.ld, ptr(m), dflt), "rebase")
+        return TimeSeriesRDD(newIndex, self.keys, p.out(out), self.partitions)
+
+    def slice(self, start, end) -> "TimeSeriesRDD":
+        """The instants in [start, end], both inclusive (date-times) -- rdd['2015-04-10':'2015-04-14'].
+        A slice that lies inside the index is a VIEW of the panel (no kernel, same row pitch), as the
+        reference's is (S/TimeSeriesUtils.scala:123-124); a uniform slice that reaches past an end
+        is rebased with NaN there (withIndex)."""
+        from . import datetimeindex as dti
+        if not _is_datetime_index(self.index):
+            raise TypeError("slice by date-time needs a DateTimeIndex (sparkts.datetimeindex)")
+        if isinstance(self.index, dti.IrregularDateTimeIndex):
+            lo, hi = self.index._slice_locs(start, end)
+            return TimeSeriesRDD(self.index.islice(lo, hi), self.keys, self.data[..., lo:hi], self.partitions)
+        target = self.index.slice(start, end)
+        if target.periods < 0:
+            target = dti.UniformDateTimeIndex(target.start, 0, target.frequency)
+        lo = dti.uniform_start_loc(self.index, target)
+        if lo >= 0 and lo + target.periods <= len(self.index):
+            return TimeSeriesRDD(target, self.keys, self.data[..., lo:lo + target.periods], self.partitions)
+        return self.withIndex(target)
+
+    def __getitem__(self, key):
+        """rdd['2015-04-10':'2015-04-14'] is slice(...); rdd['key'] is findSeries('key')."""
+        if isinstance(key, slice):
+            if key.step is not None or key.start is None or key.stop is None:
+                from .errors import IllegalArgumentException
+                raise IllegalArgumentException("a date slice needs both bounds and no step")
+            return self.slice(key.start, key.stop)
+        return self.findSeries(key)
 
     # --- S/TimeSeriesRDD.scala:188-199 ---
     def mapSeries(self, f: Callable, index=None) -> "TimeSeriesRDD":
@@ -400,12 +474,75 @@ def all_gather_results(local, group=None, gather: Optional[ResultGather] = None)
     return gather(local)
 
 
+def _is_datetime_index(index) -> bool:
+    from .datetimeindex import DateTimeIndex
+    return isinstance(index, DateTimeIndex)
+
+
+def _device_instants(index, device, stream):
+    """index.toMillisArray() as an int64 tensor on `device`: computed there for a uniform index
+    (sts_index_instants), the cached upload for an irregular one"""
+    import torch
+    inst = index._device_instants(device)
+    if inst is not None:
+        return inst
+    out = torch.empty((len(index),), dtype=torch.int64, device=device)
+    check(_native.lib().sts_index_instants(*index._c_args(), ptr(out), stream), "toMillisArray")
+    return out
+
+
+def timeSeriesRDD(targetIndex, series, device=None, defaultValue: float = float("nan")) -> TimeSeriesRDD:
+    """S/TimeSeriesRDD.scala:446-482 for series that each come with their own uniform index:
+    `series` is an iterable of (key, UniformDateTimeIndex, values).  The values are concatenated and
+    uploaded once, each series' location in `targetIndex` is computed on the host, and
+    sts_align_uniform builds the (S, len(targetIndex)) panel: every series rebased onto targetIndex,
+    `defaultValue` elsewhere.  Unequal frequencies or firsts off the target's grid raise
+    IllegalArgumentException (datetimeindex.uniform_start_loc)."""
+    import ctypes
+
+    import numpy as np
+    import torch
+
+    from . import datetimeindex as dti
+    if not isinstance(targetIndex, dti.UniformDateTimeIndex):
+        raise TypeError("timeSeriesRDD: targetIndex must be a UniformDateTimeIndex")
+    keys, rows, start = [], [], []
+    for key, index, values in series:
+        if not isinstance(index, dti.UniformDateTimeIndex):
+            raise TypeError("timeSeriesRDD: series %r needs a UniformDateTimeIndex" % (key,))
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        if v.size != len(index):
+            from .errors import IllegalArgumentException
+            raise IllegalArgumentException("timeSeriesRDD: series %r has %d values for %d instants" % (key, v.size, len(index)))
+        keys.append(key)
+        rows.append(v)
+        start.append(dti.uniform_start_loc(index, targetIndex))
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    _native.ensure_device(dev.index if dev.index is not None else torch.cuda.current_device())
+    S, T = len(keys), len(targetIndex)
+    offsets = np.zeros(S + 1, dtype=np.int64)
+    np.cumsum([r.size for r in rows], out=offsets[1:])
+    flat = np.concatenate(rows) if rows else np.empty(0, dtype=np.float64)
+    vals_d = torch.as_tensor(flat, device=dev)
+    off_d = torch.as_tensor(offsets, device=dev)
+    start_d = torch.as_tensor(np.asarray(start, dtype=np.int64), device=dev)
+    panel = torch.empty((S, T), dtype=torch.float64, device=dev)
+    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    check(_native.lib().sts_align_uniform(ptr(vals_d), ptr(off_d), ptr(start_d), S, T, ptr(panel), T,
+                                          float(defaultValue), st), "timeSeriesRDD")
+    return TimeSeriesRDD(targetIndex, keys, panel)
+
+
 def _is_uniform(index) -> bool:
-    """A UniformDateTimeIndex analogue: None (positions), a range, or instants with one
-    constant spacing (numpy datetime64 / numbers / ISO date strings)."""
+    """A UniformDateTimeIndex (any frequency: a business-day index is uniform in locations, not
+    in milliseconds) or an analogue: None (positions), a range, or instants with one constant
+    spacing (numpy datetime64 / numbers / ISO date strings)."""
     import numpy as np
     if index is None or isinstance(index, range):
         return True
+    if _is_datetime_index(index):
+        from .datetimeindex import UniformDateTimeIndex
+        return isinstance(index, UniformDateTimeIndex)
     try:
         a = np.asarray(index)
         if a.dtype.kind in "US":
