@@ -195,21 +195,12 @@ hipError_t launch_acf_wide(const double* F, int64_t S, int64_t T, int64_t ld, co
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    if (S > 65535) {   // grid.y limit: finalize in slices of series
-        for (int64_t s0 = 0; s0 < S; s0 += 65535) {
-            const int64_t n = (S - s0 < 65535) ? S - s0 : 65535;
-            hipLaunchKernelGGL(acf_wide_finalize_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)n), dim3(256), 0,
-                               st, F + s0 * ld, n, T, ld, shift ? shift + s0 : nullptr, K, nrange, nblock,
-                               part ? part + s0 * nrange * nblock * kWideStride : nullptr, acf + s0 * K, exact + s0);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-    } else {
-        hipLaunchKernelGGL(acf_wide_finalize_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)S), dim3(256), 0, st, F,
-                           S, T, ld, shift, K, nrange, nblock, part, acf, exact);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = for_series_slices(S, 65535, [&](int64_t s0, int64_t n) {   // grid.y: one series each
+        hipLaunchKernelGGL(acf_wide_finalize_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)n), dim3(256), 0, st,
+                           F + s0 * ld, n, T, ld, shift ? shift + s0 : nullptr, K, nrange, nblock,
+                           part ? part + s0 * nrange * nblock * kWideStride : nullptr, acf + s0 * K, exact + s0);
+    });
+    if (e != hipSuccess) return e;
     return launch_acf_exact(F, S, T, ld, K, exact, acf, st);
 }
 

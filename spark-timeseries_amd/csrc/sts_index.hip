@@ -8,6 +8,7 @@
 // every output element (s, j < T_out) is written exactly once by a coalesced store, nothing else is
 // written, and an input element is read only where the rule says it is copied.  No arithmetic touches
 // a value: doubles travel as 64-bit words, so every payload survives.
+#include "sts_elementwise.hpp"
 #include "sts_internal.hpp"
 #include "sts_index.hpp"
 
@@ -16,24 +17,12 @@
 namespace sts {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPerThread = 8;
-constexpr int64_t kChunk = (int64_t)kThreads * kPerThread;
 // rebase_map: a workgroup owns kMapCols map entries (one per thread) and kMapRows series
 constexpr int kMapCols = kThreads;
 constexpr int kMapRows = 64;
 // rebase_map for rows of up to kMapFlat columns: the whole map in LDS (8 KB), kMapFlatPer elements per thread
 constexpr int kMapFlat = 1024;
 constexpr int kMapFlatPer = 16;
-
-// split a logical index g in [0, S*T) into (s, t) with a double reciprocal + fix-up
-__device__ __forceinline__ void split(int64_t g, int64_t T, double rT, int64_t& s, int64_t& t) {
-    s = (int64_t)((double)g * rT);
-    int64_t b = s * T;
-    if (b > g) { s--; b -= T; }
-    else if (b + T <= g) { s++; b += T; }
-    t = g - b;
-}
 
 __global__ __launch_bounds__(kThreads) void instants_kernel(ix::Uniform u, int64_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -57,17 +46,10 @@ __global__ __launch_bounds__(kThreads) void locs_irregular_kernel(const int64_t*
 __global__ __launch_bounds__(kThreads) void shift_kernel(const uint64_t* __restrict__ in, uint64_t* __restrict__ out,
                                                          int64_t S, int64_t T_in, int64_t T_out, int64_t ld_in,
                                                          int64_t ld_out, double rT, int64_t shift, uint64_t dflt) {
-    const int64_t n = S * T_out;
-    const int64_t g0 = (int64_t)blockIdx.x * kChunk + threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < kPerThread; k++) {
-        const int64_t g = g0 + (int64_t)k * kThreads;
-        if (g >= n) break;
-        int64_t s, j;
-        split(g, T_out, rT, s, j);
+    for_each_out(S, T_out, rT, [=](int64_t s, int64_t j) {
         const int64_t m = j + shift;
         out[s * ld_out + j] = (m >= 0 && m < T_in) ? in[s * ld_in + m] : dflt;
-    }
+    });
 }
 
 // (A 16-byte form for even pitches and even shifts was measured and dropped: 1.01-1.05 x the time of
@@ -111,17 +93,10 @@ __global__ __launch_bounds__(kThreads) void map_flat_kernel(const uint64_t* __re
         sh_map[j] = (m >= 0 && m < T_in) ? m : -1;
     }
     __syncthreads();
-    const int64_t n = S * T_out;
-    const int64_t g0 = (int64_t)blockIdx.x * (kMapFlatPer * kThreads) + threadIdx.x;
-#pragma unroll 8
-    for (int k = 0; k < kMapFlatPer; k++) {
-        const int64_t g = g0 + (int64_t)k * kThreads;
-        if (g >= n) break;
-        int64_t s, j;
-        split(g, T_out, rT, s, j);
+    for_each_out<kMapFlatPer, 8>(S, T_out, rT, [=](int64_t s, int64_t j) {
         const int64_t m = sh_map[j];
         out[s * ld_out + j] = m >= 0 ? in[s * ld_in + m] : dflt;
-    }
+    });
 }
 
 // out(s, j) = values[offsets[s] + j + start_loc[s]] where 0 <= j + start_loc[s] < offsets[s + 1] -
@@ -132,23 +107,15 @@ __global__ __launch_bounds__(kThreads) void align_kernel(const uint64_t* __restr
                                                          const int64_t* __restrict__ start_loc, int64_t S, int64_t T_out,
                                                          uint64_t* __restrict__ out, int64_t ld_out, double rT,
                                                          uint64_t dflt) {
-    const int64_t n = S * T_out;
-    const int64_t g0 = (int64_t)blockIdx.x * kChunk + threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < kPerThread; k++) {
-        const int64_t g = g0 + (int64_t)k * kThreads;
-        if (g >= n) break;
-        int64_t s, j;
-        split(g, T_out, rT, s, j);
+    for_each_out(S, T_out, rT, [=](int64_t s, int64_t j) {
         const int64_t o = offsets[s], len = offsets[s + 1] - o;
         int64_t sl = start_loc[s];
         sl = sl > ix::kMaxInstant ? ix::kMaxInstant : (sl < -ix::kMaxInstant ? -ix::kMaxInstant : sl);
         const int64_t m = j + sl;
         out[s * ld_out + j] = (m >= 0 && m < len) ? values[o + m] : dflt;
-    }
+    });
 }
 
-inline dim3 grid_for(int64_t n, int64_t per_block) { return dim3((unsigned)((n + per_block - 1) / per_block)); }
 inline uint64_t bits_of(double v) {
     uint64_t b;
     __builtin_memcpy(&b, &v, sizeof b);
@@ -158,18 +125,13 @@ inline uint64_t bits_of(double v) {
 }  // namespace
 
 hipError_t launch_index_instants(const ix::Uniform& u, int64_t* out, hipStream_t st) {
-    if (u.periods <= 0) return hipSuccess;
-    hipLaunchKernelGGL(instants_kernel, grid_for(u.periods, kThreads), dim3(kThreads), 0, st, u, out);
-    return hipGetLastError();
+    return launch_elementwise(instants_kernel, u.periods, kThreads, st, u, out);
 }
 
 hipError_t launch_index_locs(const int64_t* millis, int64_t n, const ix::Uniform* u, const int64_t* instants,
                              int64_t n_instants, int64_t* loc, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    if (u) hipLaunchKernelGGL(locs_uniform_kernel, grid_for(n, kThreads), dim3(kThreads), 0, st, millis, n, *u, loc);
-    else hipLaunchKernelGGL(locs_irregular_kernel, grid_for(n, kThreads), dim3(kThreads), 0, st, millis, n, instants,
-                            n_instants, loc);
-    return hipGetLastError();
+    if (u) return launch_elementwise(locs_uniform_kernel, n, kThreads, st, millis, n, *u, loc);
+    return launch_elementwise(locs_irregular_kernel, n, kThreads, st, millis, n, instants, n_instants, loc);
 }
 
 hipError_t launch_rebase_shift(const double* in, double* out, int64_t S, int64_t T_in, int64_t T_out, int64_t ld_in,
@@ -178,35 +140,31 @@ hipError_t launch_rebase_shift(const double* in, double* out, int64_t S, int64_t
     // disjoint ranges: every shift at or past an end behaves like the nearest one, and j + shift cannot wrap
     if (shift > T_in) shift = T_in;
     if (shift < -T_out) shift = -T_out;
-    hipLaunchKernelGGL(shift_kernel, grid_for(S * T_out, kChunk), dim3(kThreads), 0, st,
-                       reinterpret_cast<const uint64_t*>(in), reinterpret_cast<uint64_t*>(out), S, T_in, T_out, ld_in,
-                       ld_out, 1.0 / (double)T_out, shift, bits_of(dflt));
-    return hipGetLastError();
+    return launch_elementwise(shift_kernel, S * T_out, kChunk, st, reinterpret_cast<const uint64_t*>(in),
+                              reinterpret_cast<uint64_t*>(out), S, T_in, T_out, ld_in, ld_out, 1.0 / (double)T_out, shift,
+                              bits_of(dflt));
 }
 
 hipError_t launch_rebase_map(const double* in, double* out, int64_t S, int64_t T_in, int64_t T_out, int64_t ld_in,
                              int64_t ld_out, const int64_t* map, double dflt, hipStream_t st) {
     if (S <= 0 || T_out <= 0) return hipSuccess;
-    if (T_out <= kMapFlat) {
-        hipLaunchKernelGGL(map_flat_kernel, grid_for(S * T_out, (int64_t)kMapFlatPer * kThreads), dim3(kThreads), 0, st,
-                           reinterpret_cast<const uint64_t*>(in), reinterpret_cast<uint64_t*>(out), S, T_in, T_out, ld_in,
-                           ld_out, 1.0 / (double)T_out, map, bits_of(dflt));
-        return hipGetLastError();
-    }
+    const uint64_t* x = reinterpret_cast<const uint64_t*>(in);
+    uint64_t* y = reinterpret_cast<uint64_t*>(out);
+    if (T_out <= kMapFlat)
+        return launch_elementwise(map_flat_kernel, S * T_out, (int64_t)kMapFlatPer * kThreads, st, x, y, S, T_in, T_out,
+                                  ld_in, ld_out, 1.0 / (double)T_out, map, bits_of(dflt));
+    // one workgroup per tile
     const int64_t col_tiles = (T_out + kMapCols - 1) / kMapCols, row_tiles = (S + kMapRows - 1) / kMapRows;
-    hipLaunchKernelGGL(map_kernel, dim3((unsigned)(col_tiles * row_tiles)), dim3(kThreads), 0, st,
-                       reinterpret_cast<const uint64_t*>(in), reinterpret_cast<uint64_t*>(out), S, T_in, T_out, ld_in,
-                       ld_out, col_tiles, 1.0 / (double)col_tiles, map, bits_of(dflt));
-    return hipGetLastError();
+    return launch_elementwise(map_kernel, col_tiles * row_tiles, 1, st, x, y, S, T_in, T_out, ld_in, ld_out, col_tiles,
+                              1.0 / (double)col_tiles, map, bits_of(dflt));
 }
 
 hipError_t launch_align_uniform(const double* values, const int64_t* offsets, const int64_t* start_loc, int64_t S,
                                 int64_t T_out, double* out, int64_t ld_out, double dflt, hipStream_t st) {
     if (S <= 0 || T_out <= 0) return hipSuccess;
-    hipLaunchKernelGGL(align_kernel, grid_for(S * T_out, kChunk), dim3(kThreads), 0, st,
-                       reinterpret_cast<const uint64_t*>(values), offsets, start_loc, S, T_out,
-                       reinterpret_cast<uint64_t*>(out), ld_out, 1.0 / (double)T_out, bits_of(dflt));
-    return hipGetLastError();
+    return launch_elementwise(align_kernel, S * T_out, kChunk, st, reinterpret_cast<const uint64_t*>(values), offsets,
+                              start_loc, S, T_out, reinterpret_cast<uint64_t*>(out), ld_out, 1.0 / (double)T_out,
+                              bits_of(dflt));
 }
 
 }  // namespace sts

@@ -141,11 +141,9 @@ __global__ __launch_bounds__(256) void fill_nan_kernel(double* panel, int64_t S,
 
 template <typename F>
 hipError_t per_series_grid(int64_t S, int64_t T, F&& launch) {
-    for (int64_t s = 0; s < S; s += 65535) {
-        const int64_t n = (S - s < 65535) ? S - s : 65535;
+    return for_series_slices(S, 65535, [&](int64_t s, int64_t n) {
         launch(s, dim3((unsigned)((T + 255) / 256), (unsigned)n));
-    }
-    return hipGetLastError();
+    });
 }
 
 }  // namespace

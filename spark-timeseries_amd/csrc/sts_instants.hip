@@ -378,23 +378,17 @@ hipError_t launch_series_stats(const double* in, double* out, int64_t S, int64_t
 
 hipError_t launch_nan_instants(const double* in, uint8_t* flags, int64_t S, int64_t T, int64_t ld, hipStream_t st) {
     if (S <= 0 || T <= 0) return hipSuccess;
-    const int64_t gy = (S + kNanSeries - 1) / kNanSeries;
-    if (gy > 65535) {   // grid.y limit: split the series range
-        for (int64_t s = 0; s < S; s += 65535LL * kNanSeries) {
-            const int64_t n = (S - s < 65535LL * kNanSeries) ? S - s : 65535LL * kNanSeries;
-            hipError_t e = launch_nan_instants(in + s * ld, flags, n, T, ld, st);
-            if (e != hipSuccess) return e;
+    return for_series_slices(S, 65535LL * kNanSeries, [&](int64_t s0, int64_t n) {   // grid.y: groups of kNanSeries
+        const double* x = in + s0 * ld;
+        const unsigned gy = (unsigned)((n + kNanSeries - 1) / kNanSeries);
+        if (T % 2 == 0 && ld % 2 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0) {
+            dim3 grid((unsigned)((T / 2 + kNanT - 1) / kNanT), gy);
+            hipLaunchKernelGGL(nan_instants16_kernel, grid, dim3(kNanT), 0, st, x, flags, n, T, ld);
+        } else {
+            dim3 grid((unsigned)((T + kNanT - 1) / kNanT), gy);
+            hipLaunchKernelGGL(nan_instants_kernel, grid, dim3(kNanT), 0, st, x, flags, n, T, ld);
         }
-        return hipSuccess;
-    }
-    if (T % 2 == 0 && ld % 2 == 0 && reinterpret_cast<uintptr_t>(in) % 16 == 0) {
-        dim3 grid((unsigned)((T / 2 + kNanT - 1) / kNanT), (unsigned)gy);
-        hipLaunchKernelGGL(nan_instants16_kernel, grid, dim3(kNanT), 0, st, in, flags, S, T, ld);
-        return hipGetLastError();
-    }
-    dim3 grid((unsigned)((T + kNanT - 1) / kNanT), (unsigned)gy);
-    hipLaunchKernelGGL(nan_instants_kernel, grid, dim3(kNanT), 0, st, in, flags, S, T, ld);
-    return hipGetLastError();
+    });
 }
 
 int64_t active_scratch_elems(int64_t T) { return (T + kCompact - 1) / kCompact + 1; }
@@ -424,15 +418,13 @@ hipError_t launch_transpose(const double* in, double* out, int64_t S, int64_t T,
     if (S <= 0 || T <= 0) return hipSuccess;
     const bool v16 = (T % 2 == 0) && (S % 2 == 0) && (ld_in % 2 == 0) && (ld_out % 2 == 0) &&
                      (reinterpret_cast<uintptr_t>(in) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-    for (int64_t s = 0; s < S; s += 64LL * 65535) {
-        const int64_t n = (S - s < 64LL * 65535) ? S - s : 64LL * 65535;
+    return for_series_slices(S, 64LL * 65535, [&](int64_t s, int64_t n) {   // grid.y: tiles of 64 series
         dim3 grid((unsigned)((T + 63) / 64), (unsigned)((n + 63) / 64));
         if (v16)
             hipLaunchKernelGGL(transpose16_kernel, grid, dim3(256), 0, st, in + s * ld_in, out + s, n, T, ld_in, ld_out);
         else
             hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, st, in + s * ld_in, out + s, n, T, ld_in, ld_out);
-    }
-    return hipGetLastError();
+    });
 }
 
 }  // namespace sts

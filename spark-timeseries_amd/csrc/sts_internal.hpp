@@ -81,6 +81,19 @@ int validate(F&& f, bool* has_work) {
     return validate_call([](void* c) { return (*static_cast<F*>(c))(); }, static_cast<void*>(&f), has_work);
 }
 
+// A series range that one launch cannot hold (a grid's y dimension ends at 65 535): launch(s0, n)
+// enqueues series s0 .. s0 + n of consecutive slices of at most max_per_launch series; every
+// slice's launch is checked, and the first error ends the loop.
+template <class F>
+hipError_t for_series_slices(int64_t S, int64_t max_per_launch, F&& launch) {
+    for (int64_t s0 = 0; s0 < S; s0 += max_per_launch) {
+        launch(s0, S - s0 < max_per_launch ? S - s0 : max_per_launch);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // launchers (return hipError_t of the launch)
 hipError_t launch_tile(int method, int tw, const TileArgs& a, hipStream_t st);
 hipError_t launch_acf_finalize(const FinalizeArgs& a, hipStream_t st);

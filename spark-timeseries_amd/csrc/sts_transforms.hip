@@ -9,6 +9,7 @@
 // steps, every output element is written exactly once by a coalesced store, and only elements
 // (s, t < T) are read.  The library is built with -ffp-contract=off and without fast-math, so
 // a / b is the IEEE division and a / b - 1.0 stays a division and a subtraction.
+#include "sts_elementwise.hpp"
 #include "sts_internal.hpp"
 
 #include <hip/hip_runtime.h>
@@ -16,87 +17,45 @@
 namespace sts {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPerThread = 8;
-constexpr int64_t kChunk = (int64_t)kThreads * kPerThread;
 constexpr int kWaves = kThreads / 64;   // wave-per-series kernels: series per workgroup
-
-// split a logical index g in [0, S*T) into (s, t) with a double reciprocal + fix-up
-__device__ __forceinline__ void split(int64_t g, int64_t T, double rT, int64_t& s, int64_t& t) {
-    s = (int64_t)((double)g * rT);
-    int64_t b = s * T;
-    if (b > g) { s--; b -= T; }
-    else if (b + T <= g) { s++; b += T; }
-    t = g - b;
-}
 
 // ret(i) = ts(i + lag) / ts(i) [- 1.0], i < To = T - lag
 __global__ __launch_bounds__(kThreads) void quotients_kernel(const double* __restrict__ in, double* __restrict__ out,
                                                              int64_t S, int64_t To, int64_t ld_in, int64_t ld_out,
                                                              double rTo, int lag, bool minus_one) {
-    const int64_t n = S * To;
-    const int64_t g0 = (int64_t)blockIdx.x * kChunk + threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < kPerThread; j++) {
-        const int64_t g = g0 + (int64_t)j * kThreads;
-        if (g >= n) break;
-        int64_t s, i;
-        split(g, To, rTo, s, i);
+    for_each_out(S, To, rTo, [=](int64_t s, int64_t i) {
         const double* x = in + s * ld_in;
         const double q = x[i + lag] / x[i];
         out[s * ld_out + i] = minus_one ? q - 1.0 : q;
-    }
+    });
 }
 
 // result(i) = if (result(i).isNaN) filler else result(i); in place allowed (element-wise)
 __global__ __launch_bounds__(kThreads) void fill_default_kernel(const double* in, double* out, int64_t S, int64_t T,
                                                                 int64_t ld_in, int64_t ld_out, double rT, double filler) {
-    const int64_t n = S * T;
-    const int64_t g0 = (int64_t)blockIdx.x * kChunk + threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < kPerThread; j++) {
-        const int64_t g = g0 + (int64_t)j * kThreads;
-        if (g >= n) break;
-        int64_t s, t;
-        split(g, T, rT, s, t);
+    for_each_out(S, T, rT, [=](int64_t s, int64_t t) {
         const double v = in[s * ld_in + t];
         out[s * ld_out + t] = (v != v) ? filler : v;
-    }
+    });
 }
 
 // sampledValues(j) = values(phase + j * n), j < To
 __global__ __launch_bounds__(kThreads) void downsample_kernel(const double* __restrict__ in, double* __restrict__ out,
                                                               int64_t S, int64_t To, int64_t ld_in, int64_t ld_out,
                                                               double rTo, int n, int phase) {
-    const int64_t tot = S * To;
-    const int64_t g0 = (int64_t)blockIdx.x * kChunk + threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < kPerThread; j++) {
-        const int64_t g = g0 + (int64_t)j * kThreads;
-        if (g >= tot) break;
-        int64_t s, i;
-        split(g, To, rTo, s, i);
-        out[s * ld_out + i] = in[s * ld_in + phase + i * n];
-    }
+    for_each_out(S, To, rTo, [=](int64_t s, int64_t i) { out[s * ld_out + i] = in[s * ld_in + phase + i * n]; });
 }
 
 // sampledValues(phase + j * n) = values(j), the filler elsewhere; i < To = T * n, so (i - phase) / n < T
 __global__ __launch_bounds__(kThreads) void upsample_kernel(const double* __restrict__ in, double* __restrict__ out,
                                                             int64_t S, int64_t To, int64_t ld_in, int64_t ld_out,
                                                             double rTo, int n, int phase, double filler) {
-    const int64_t tot = S * To;
-    const int64_t g0 = (int64_t)blockIdx.x * kChunk + threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < kPerThread; j++) {
-        const int64_t g = g0 + (int64_t)j * kThreads;
-        if (g >= tot) break;
-        int64_t s, i;
-        split(g, To, rTo, s, i);
+    for_each_out(S, To, rTo, [=](int64_t s, int64_t i) {
         const int64_t k = i - phase;
         const int64_t q = k / n;
         const bool hit = k >= 0 && q * n == k;
         out[s * ld_out + i] = hit ? in[s * ld_in + q] : filler;
-    }
+    });
 }
 
 __device__ __forceinline__ unsigned long long lanes_upto(int lane) {   // bits 0..lane
@@ -183,7 +142,6 @@ __global__ __launch_bounds__(kThreads) void first_last_kernel(const double* __re
     }
 }
 
-inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kChunk - 1) / kChunk)); }
 inline dim3 grid_waves(int64_t S) { return dim3((unsigned)((S + kWaves - 1) / kWaves)); }
 
 }  // namespace
@@ -192,9 +150,8 @@ hipError_t launch_quotients(const double* in, double* out, int64_t S, int64_t T,
                             bool minus_one, hipStream_t st) {
     const int64_t To = T - lag;
     if (S <= 0 || To <= 0) return hipSuccess;
-    hipLaunchKernelGGL(quotients_kernel, grid_for(S * To), dim3(kThreads), 0, st, in, out, S, To, ld_in, ld_out,
-                       1.0 / (double)To, lag, minus_one);
-    return hipGetLastError();
+    return launch_elementwise(quotients_kernel, S * To, kChunk, st, in, out, S, To, ld_in, ld_out, 1.0 / (double)To, lag,
+                              minus_one);
 }
 
 hipError_t launch_fill_prev_quotients(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out,
@@ -208,26 +165,22 @@ hipError_t launch_fill_prev_quotients(const double* in, double* out, int64_t S, 
 
 hipError_t launch_fill_default(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out,
                                double filler, hipStream_t st) {
-    if (S * T <= 0) return hipSuccess;
-    hipLaunchKernelGGL(fill_default_kernel, grid_for(S * T), dim3(kThreads), 0, st, in, out, S, T, ld_in, ld_out,
-                       1.0 / (double)T, filler);
-    return hipGetLastError();
+    return launch_elementwise(fill_default_kernel, S * T, kChunk, st, in, out, S, T, ld_in, ld_out, 1.0 / (double)T,
+                              filler);
 }
 
 hipError_t launch_downsample(const double* in, double* out, int64_t S, int64_t T_out, int64_t ld_in, int64_t ld_out, int n,
                              int phase, hipStream_t st) {
     if (S <= 0 || T_out <= 0) return hipSuccess;
-    hipLaunchKernelGGL(downsample_kernel, grid_for(S * T_out), dim3(kThreads), 0, st, in, out, S, T_out, ld_in, ld_out,
-                       1.0 / (double)T_out, n, phase);
-    return hipGetLastError();
+    return launch_elementwise(downsample_kernel, S * T_out, kChunk, st, in, out, S, T_out, ld_in, ld_out,
+                              1.0 / (double)T_out, n, phase);
 }
 
 hipError_t launch_upsample(const double* in, double* out, int64_t S, int64_t T_out, int64_t ld_in, int64_t ld_out, int n,
                            int phase, double filler, hipStream_t st) {
     if (S <= 0 || T_out <= 0) return hipSuccess;
-    hipLaunchKernelGGL(upsample_kernel, grid_for(S * T_out), dim3(kThreads), 0, st, in, out, S, T_out, ld_in, ld_out,
-                       1.0 / (double)T_out, n, phase, filler);
-    return hipGetLastError();
+    return launch_elementwise(upsample_kernel, S * T_out, kChunk, st, in, out, S, T_out, ld_in, ld_out,
+                              1.0 / (double)T_out, n, phase, filler);
 }
 
 hipError_t launch_first_last(const double* in, int64_t S, int64_t T, int64_t ld, int64_t* first, int64_t* last,

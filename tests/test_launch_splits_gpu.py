@@ -1,14 +1,15 @@
 """The launch paths that only very large S reaches (a grid dimension's 65 535 limit), each at a
 tiny T so that the panel stays small.  Needs an MI355X.
 
-  launch_acf_wide's grid.y slice loop       S = 65 541 > 65 535, K = 64       (sts_acf_wide.hip)
-  launch_nan_instants' recursion,
-  launch_transpose's slice loop             S > 64 * 65 535 = 4 194 240       (sts_instants.hip)
+  launch_acf_wide's finalize slices         S = 65 541 > 65 535, K = 64       (sts_acf_wide.hip)
+  launch_nan_instants' and
+  launch_transpose's slices                 S > 64 * 65 535 = 4 194 240       (sts_instants.hip)
   gen_grid's z dimension                    S = 131 073: three z-slices       (sts_gen.hip)
-  per_series_grid                           S > 65 535: fill_nan_kernel of sts_observations_to_panel,
+  per_series_grid's slices                  S > 65 535: fill_nan_kernel of sts_observations_to_panel,
                                             wire decode / encode past kRowT = 4096 (sts_ingest.hip)
 
-Each path is a few lines of pointer arithmetic per slice (F + s0 * ld, acf + s0 * K, out + s ...),
+All but gen_grid walk the series range with for_series_slices (sts_internal.hpp); what differs is the
+lambda each hands it.  Each path is a few lines of pointer arithmetic per slice (F + s0 * ld, acf + s0 * K, out + s ...),
 where one wrong offset gives plausible numbers: the data is built so that every row's expected
 result is known on the device -- a tiling (row s equals row s mod 64 / mod 8), a formula
 (x[s, t] = 8 s + t, exact in binary64) or the bit-exact CPU generator -- outputs are pre-filled with
