@@ -26,6 +26,7 @@
 // only end in TooManyEvaluationsException: that is decided after the first pass.
 #include "sts_ewma_opt.hpp"
 #include "sts_internal.hpp"
+#include "sts_lane_rows.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -64,22 +65,16 @@ struct SseGrad {
     }
 };
 
-// One wave = SPW series (lanes < SPW), CH-step chunks through LDS.  Each round every lane
-// with a pending request evaluates sse and gradient at its own smoothing value; FIT = false
-// is the plain sse / gradient operator (one round at smoothing[s]).
+// One wave = SPW series (lanes < SPW), CH-step chunks through LDS (stream_rows, sts_lane_rows.hpp).
+// Each round every lane with a pending request evaluates sse and gradient at its own smoothing
+// value; FIT = false is the plain sse / gradient operator (one round at smoothing[s]).
 template <int SPW, int CH, bool FIT>
 __global__ __launch_bounds__(64) void ewma_fit_kernel(EwmaFitArgs a) {
-    constexpr int kRow = CH + 1;
-    constexpr int NLD = SPW * CH / 64;
-    static_assert(SPW * CH % 64 == 0 && (CH % 64 == 0 || 64 % CH == 0), "chunk shape: whole load instructions");
-    __shared__ double tile[SPW * kRow];
-    const int lane = threadIdx.x;
-    const int64_t s0 = (int64_t)blockIdx.x * SPW;
-    const int64_t sl = s0 + lane;
-    const bool live = lane < SPW && sl < a.S;
-    const int ns = (a.S - s0 < SPW) ? (int)(a.S - s0) : SPW;
+    __shared__ double tile[LaneRows<SPW, CH>::kTile];
+    const LaneBlock<SPW> b(a.S);
+    const int64_t sl = b.sl;
+    const bool live = b.live;
     const int64_t T = a.T;
-    const double* base = a.in + s0 * a.ld;
 
     EwmaOpt o;
     ewma_init(o);
@@ -96,32 +91,10 @@ __global__ __launch_bounds__(64) void ewma_fit_kernel(EwmaFitArgs a) {
         const double s = o.req, oms = 1.0 - s;
         SseGrad g;
         g.start(0.0);
-        double pre[NLD];
-        auto fetch = [&](int64_t tc) {
-#pragma unroll
-            for (int i = 0; i < NLD; i++) {
-                const int row = (i * 64 + lane) / CH, col = (i * 64 + lane) % CH;
-                const bool want_row = row < ns && ((want >> row) & 1ull);
-                pre[i] = (want_row && tc + col < T) ? base[row * a.ld + tc + col] : 0.0;
-            }
-        };
-        fetch(0);
-        for (int64_t tc = 0; tc < T; tc += CH) {
-            const int len = (T - tc < CH) ? (int)(T - tc) : CH;
-#pragma unroll
-            for (int i = 0; i < NLD; i++) {
-                const int row = (i * 64 + lane) / CH, col = (i * 64 + lane) % CH;
-                tile[row * kRow + col] = pre[i];
-            }
-            if (tc + CH < T) fetch(tc + CH);   // next chunk in flight during this one
-            __syncthreads();
-            if (pending) {
-                const double* myrow = tile + lane * kRow;
-                if (tc == 0) g.start(myrow[0]);
-                g.run(myrow, tc == 0 ? 1 : 0, len, s, oms);
-            }
-            __syncthreads();
-        }
+        stream_rows<SPW, CH>(tile, a.in + b.s0 * a.ld, a.ld, T, b.ns, want, pending, [&](const double* myrow, int64_t tc, int len) {
+            if (tc == 0) g.start(myrow[0]);
+            g.run(myrow, tc == 0 ? 1 : 0, len, s, oms);
+        });
         if (pending) {
             o.res_f = g.sq;
             o.res_g = 2 * g.dJ;
@@ -159,11 +132,8 @@ constexpr int kFitCh = STS_EWMA_CH;
 }  // namespace
 
 hipError_t launch_ewma_fit(const EwmaFitArgs& a, bool fit, hipStream_t st) {
-    if (a.S <= 0) return hipSuccess;
-    dim3 grid((unsigned)((a.S + kFitSpw - 1) / kFitSpw)), block(64);
-    if (fit) hipLaunchKernelGGL((ewma_fit_kernel<kFitSpw, kFitCh, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((ewma_fit_kernel<kFitSpw, kFitCh, false>), grid, block, 0, st, a);
-    return hipGetLastError();
+    if (fit) return launch_lane_rows(ewma_fit_kernel<kFitSpw, kFitCh, true>, a.S, kFitSpw, st, a);
+    return launch_lane_rows(ewma_fit_kernel<kFitSpw, kFitCh, false>, a.S, kFitSpw, st, a);
 }
 
 }  // namespace sts

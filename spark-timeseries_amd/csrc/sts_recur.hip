@@ -18,6 +18,7 @@
 //    transposed so each lane runs its series' recurrence over the chunk in registers.
 #include "sts_internal.hpp"
 #include "sts_dma.hpp"
+#include "sts_lane_rows.hpp"
 #include "sts_lanes.hpp"
 
 #include <hip/hip_runtime.h>
@@ -30,7 +31,8 @@
 namespace sts {
 namespace {
 
-constexpr int kSpw = STS_FDE_SPW, kCh = STS_FDE_CH;
+constexpr int kSpw = STS_FDE_SPW, kCh = STS_FDE_CH;   // the 16-byte kernel's shape
+constexpr int kSpw8 = 64, kCh8 = 32;                   // the 8-byte kernel's
 // recur_row_kernel's launch shape (C2 A/B, profiles/r04_v9_ab_c2_lps.jsonl, r04_v10_ab_c2_shape.jsonl):
 // 16 / 32 / 64 lanes per series 1.176-1.185 / 1.162-1.170 / 1.173-1.177 ms; 1 / 2 / 4 waves per
 // workgroup 1.248-1.252 / 1.202-1.204 / 1.170-1.174 ms; XCD-contiguous spans 1.068-1.070 against
@@ -163,88 +165,27 @@ struct RecurLane {
     }
 };
 
-// SPW series per wave, CH steps per chunk: the chunk's SPW x CH block moves through LDS
-// with every load / store instruction covering 64 consecutive steps of ONE series (512
-// contiguous bytes); lanes < SPW then run their series' recurrence over the chunk.
-// Longer row segments (fewer series, longer chunks) keep HBM pages open: C2's 1M series
+// SPW series per wave, CH steps per chunk through LDS (map_rows, sts_lane_rows.hpp); lanes < SPW
+// run their series' recurrence over the chunk.  Longer row segments (fewer series, longer chunks) keep HBM pages open: C2's 1M series
 // x 390 steps are only 3 KB each.
-template <int OP, int H, int SPW = 64, int CH = 32, bool V2 = false>
+template <int OP, int H, int SPW, int CH, bool V2 = false>
 __global__ __launch_bounds__(64) void recur_kernel(RecurArgs a) {
-    // V2: 16-B loads / stores (two consecutive steps per lane, half the memory instructions);
-    // rows padded to an even stride so the 16-B LDS accesses stay aligned
+    // V2: 16-B loads / stores (two consecutive steps per lane, half the memory instructions;
+    // map_rows' EPL = 2)
     // (round 4: 130-step chunks -- three for C2's 390 steps instead of 3 x 128 + 6 -- ran 2.14
     // against 1.43 ms: a 130-step row does not fill whole 128-double load instructions, so every
     // instruction then spans two rows; profiles/r04_v4_ab_c2.jsonl)
-    constexpr int kRow = V2 ? CH + 2 : CH + 1;
     constexpr int EPL = V2 ? 2 : 1;               // elements per lane per instruction
-    constexpr int NLD = SPW * CH / (64 * EPL);    // load instructions per chunk per lane
-    static_assert(SPW * CH % (64 * EPL) == 0 && (V2 ? CH % 2 == 0 : (CH % 64 == 0 || 64 % CH == 0)), "chunk shape");
-    __shared__ __attribute__((aligned(16))) double tile[SPW * kRow];
-    const int lane = threadIdx.x;
-    const int64_t s0 = (int64_t)blockIdx.x * SPW;
-    const int64_t sl = s0 + lane;                 // this lane's series (lanes < SPW)
-    const bool live = lane < SPW && sl < a.S;
-    const int ns = (a.S - s0 < SPW) ? (int)(a.S - s0) : SPW;
-    const int64_t T = a.T;
+    __shared__ __attribute__((aligned(16))) double tile[LaneRows<SPW, CH, EPL>::kTile];
+    const LaneBlock<SPW> b(a.S);
 
     RecurLane<OP, H> rl;
-    rl.init(a, sl, live);
+    rl.init(a, b.sl, b.live);
 
-    // load instruction i of a chunk: element e = (i * 64 + lane) * EPL, row e / CH, column e % CH
-    double2 pre[NLD];
-    auto fetch = [&](int64_t tc) {
-        const int len = (T - tc < CH) ? (int)(T - tc) : CH;
-#pragma unroll
-        for (int i = 0; i < NLD; i++) {
-            const int e = (i * 64 + lane) * EPL;
-            const int row = e / CH, col = e % CH;
-            const double* src = a.in + (s0 + row) * a.ld_in + tc + col;
-            if (V2) {
-                if (row < ns && col + 1 < len) {
-                    pre[i] = *reinterpret_cast<const double2*>(src);
-                } else {
-                    pre[i].x = (row < ns && col < len) ? src[0] : 0.0;
-                    pre[i].y = 0.0;
-                }
-            } else {
-                pre[i].x = (row < ns && col < len) ? src[0] : 0.0;
-            }
-        }
-    };
-    fetch(0);
-    for (int64_t tc = 0; tc < T; tc += CH) {
-        const int len = (T - tc < CH) ? (int)(T - tc) : CH;
-#pragma unroll
-        for (int i = 0; i < NLD; i++) {
-            const int e = (i * 64 + lane) * EPL;
-            const int row = e / CH, col = e % CH;
-            if (V2) {
-                if (row < ns && col < len) *reinterpret_cast<double2*>(&tile[row * kRow + col]) = pre[i];
-            } else {
-                if (row < ns && col < len) tile[row * kRow + col] = pre[i].x;
-            }
-        }
-        if (tc + CH < T) fetch(tc + CH);   // next chunk in flight during this one
-        __syncthreads();
-        if (live) {
-            double* myrow = tile + lane * kRow;
-            for (int c = 0; c < len; c++) myrow[c] = rl.step(myrow[c], tc + c);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < NLD; i++) {
-            const int e = (i * 64 + lane) * EPL;
-            const int row = e / CH, col = e % CH;
-            double* d = a.out + (s0 + row) * a.ld_out + tc + col;
-            if (V2) {
-                if (row < ns && col + 1 < len) *reinterpret_cast<double2*>(d) = *reinterpret_cast<const double2*>(&tile[row * kRow + col]);
-                else if (row < ns && col < len) d[0] = tile[row * kRow + col];
-            } else {
-                if (row < ns && col < len) d[0] = tile[row * kRow + col];
-            }
-        }
-        __syncthreads();
-    }
+    map_rows<SPW, CH, EPL>(tile, a.in, a.ld_in, a.out, a.ld_out, a.T, b.s0, b.ns, b.live,
+                           [&](double* myrow, int64_t tc, int len) {
+        for (int c = 0; c < len; c++) myrow[c] = rl.step(myrow[c], tc + c);
+    });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -577,21 +518,18 @@ hipError_t launch_h(const RecurArgs& a, int need, hipStream_t st) {
     }
 chunks:
     if (need <= 8 && rows16(a)) {   // the C2 shape: 16 series x 128-step chunks, 16-B accesses
-        dim3 g((unsigned)((a.S + kSpw - 1) / kSpw)), b(64);
-        if (need <= 1) hipLaunchKernelGGL((recur_kernel<OP, 1, kSpw, kCh, true>), g, b, 0, st, a);
-        else if (need <= 2) hipLaunchKernelGGL((recur_kernel<OP, 2, kSpw, kCh, true>), g, b, 0, st, a);
-        else if (need <= 4) hipLaunchKernelGGL((recur_kernel<OP, 4, kSpw, kCh, true>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((recur_kernel<OP, 8, kSpw, kCh, true>), g, b, 0, st, a);
-        return hipGetLastError();
+        if (need <= 1) return launch_lane_rows(recur_kernel<OP, 1, kSpw, kCh, true>, a.S, kSpw, st, a);
+        if (need <= 2) return launch_lane_rows(recur_kernel<OP, 2, kSpw, kCh, true>, a.S, kSpw, st, a);
+        if (need <= 4) return launch_lane_rows(recur_kernel<OP, 4, kSpw, kCh, true>, a.S, kSpw, st, a);
+        return launch_lane_rows(recur_kernel<OP, 8, kSpw, kCh, true>, a.S, kSpw, st, a);
     }
-    dim3 grid((unsigned)((a.S + 63) / 64)), block(64);
-    if (need <= 1) hipLaunchKernelGGL((recur_kernel<OP, 1>), grid, block, 0, st, a);
-    else if (need <= 2) hipLaunchKernelGGL((recur_kernel<OP, 2>), grid, block, 0, st, a);
-    else if (need <= 4) hipLaunchKernelGGL((recur_kernel<OP, 4>), grid, block, 0, st, a);
-    else if (need <= 8) hipLaunchKernelGGL((recur_kernel<OP, 8>), grid, block, 0, st, a);
-    else if (need <= 16) hipLaunchKernelGGL((recur_kernel<OP, 16>), grid, block, 0, st, a);
-    else if (need <= 32) hipLaunchKernelGGL((recur_kernel<OP, 32>), grid, block, 0, st, a);
-    else if (OP == kArAdd || OP == kArRemoveInplace)
+    if (need <= 1) return launch_lane_rows(recur_kernel<OP, 1, kSpw8, kCh8>, a.S, kSpw8, st, a);
+    if (need <= 2) return launch_lane_rows(recur_kernel<OP, 2, kSpw8, kCh8>, a.S, kSpw8, st, a);
+    if (need <= 4) return launch_lane_rows(recur_kernel<OP, 4, kSpw8, kCh8>, a.S, kSpw8, st, a);
+    if (need <= 8) return launch_lane_rows(recur_kernel<OP, 8, kSpw8, kCh8>, a.S, kSpw8, st, a);
+    if (need <= 16) return launch_lane_rows(recur_kernel<OP, 16, kSpw8, kCh8>, a.S, kSpw8, st, a);
+    if (need <= 32) return launch_lane_rows(recur_kernel<OP, 32, kSpw8, kCh8>, a.S, kSpw8, st, a);
+    if (OP == kArAdd || OP == kArRemoveInplace)
         hipLaunchKernelGGL((ar_naive_kernel<OP>), dim3((unsigned)((a.S + 255) / 256)), dim3(256), 0, st, a);
     else if (OP == kDiffInplace)
         hipLaunchKernelGGL(diff_chain_kernel, dim3((unsigned)((a.S * a.lag + 255) / 256)), dim3(256), 0, st,
