@@ -1753,6 +1753,103 @@ int sts_bg_test(const double* resid, int64_t S, int64_t T, int64_t ld, const dou
     return bgbp_test(false, resid, S, T, ld, factors, k, ld_f, fs, max_lag, stat, pvalue, err_per_series, stream);
 }
 
+// ---- include/sts_regress.h ----
+
+// the factor panel of t5 / t6: k, ld_f, fs and the pointer
+static int factor_panel(const double* factors, int64_t S, int64_t T, int k, int64_t ld_f, int64_t fs, const char* name) {
+    if (k < 1 || k > sts::kMaxFactors)
+        return fail(STS_ERR_BAD_ARG, "%s: %d factors outside [1, %d]", name, k, sts::kMaxFactors);
+    if (ld_f < T)
+        return fail(STS_ERR_BAD_ARG, "%s: factor leading dimension %lld < T=%lld", name, (long long)ld_f, (long long)T);
+    if (fs != 0 && fs < (int64_t)(k - 1) * ld_f + T)
+        return fail(STS_ERR_BAD_ARG, "%s: factor series stride %lld overlaps (needs 0 or >= %lld)", name, (long long)fs,
+                    (long long)((int64_t)(k - 1) * ld_f + T));
+    if (S * T > 0 && !factors) return fail(STS_ERR_BAD_ARG, "%s: null factor pointer", name);
+    return STS_OK;
+}
+
+// g1.  Scratch as bgtest / bptest: one basis for shared factors, per-series factors in chunks of
+// series whose bases fit kBasisChunkBytes, none where the kernel builds each basis in LDS.
+int sts_factor_ols(const double* y, int64_t S, int64_t T, int64_t ld, const double* factors, int k, int64_t ld_f,
+                   int64_t fs, double* beta, int64_t ld_b, double* stderr_out, double* stats, double* resid, int64_t ld_r,
+                   int32_t* err_per_series, void* stream) {
+    const char* name = "factor_ols";
+    int r;
+    if ((r = factor_panel(factors, S, T, k, ld_f, fs, name))) return r;
+    if ((r = stat_panel(y, S, T, ld, beta, name))) return r;
+    if (ld_b < (int64_t)k + 1)
+        return fail(STS_ERR_BAD_ARG, "%s: coefficient leading dimension %lld < k + 1 = %d", name, (long long)ld_b, k + 1);
+    if (resid && ld_r < T)
+        return fail(STS_ERR_BAD_ARG, "%s: residual leading dimension %lld < T=%lld", name, (long long)ld_r, (long long)T);
+    if (resid && resid == y && S > 0) return fail(STS_ERR_BAD_ARG, "%s: resid must not alias y", name);
+    if (T <= (int64_t)k + 1)
+        return fail(STS_ERR_NOT_ENOUGH_DATA, "%s: not enough data (%lld rows) for the number of predictors (%d)", name,
+                    (long long)T, k + 1);
+    if (S == 0) return STS_OK;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    ErrSink es(err_per_series, S, st);
+    if ((r = es.prepare())) return r;
+    sts::OlsArgs a{};
+    a.y = y; a.S = S; a.T = T; a.ld = ld; a.factors = factors; a.ld_f = ld_f; a.fs = fs; a.k = k;
+    a.beta = beta; a.se = stderr_out; a.ld_b = ld_b; a.stats = stats; a.resid = resid; a.ld_r = ld_r; a.err = es.dev;
+    const bool own = sts::ols_regime(T, k, fs) == 2;
+    const size_t per_basis = ((size_t)k * (size_t)T + sts::kOlsAux) * sizeof(double);
+    int64_t chunk = 1;
+    if (own) chunk = S;
+    else if (fs != 0) chunk = std::max<int64_t>(1, std::min<int64_t>(S, (int64_t)(kBasisChunkBytes / per_basis)));
+    const size_t nbasis = own ? 0 : (size_t)chunk;
+    Scratch sc(st);
+    HIP_TRY(sc.alloc(per_basis * nbasis), "hipMallocAsync(factor basis)");
+    a.basis = static_cast<double*>(sc.p);
+    a.aux = a.basis + (size_t)k * (size_t)T * nbasis;
+    if (fs == 0) {
+        HIP_TRY(sts::launch_ols_basis(a, 0, 1, st), name);
+        HIP_TRY(timed(st, [&] { return sts::launch_ols(a, 0, S, st); }), name);
+    } else {
+        a.basis_stride = (int64_t)k * T;
+        a.aux_stride = sts::kOlsAux;
+        for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+            const int64_t ns = std::min<int64_t>(chunk, S - s0);
+            HIP_TRY(sts::launch_ols_basis(a, s0, ns, st), name);
+            HIP_TRY(timed(st, [&] { return sts::launch_ols(a, s0, ns, st); }), name);
+        }
+    }
+    return es.finish(name);
+}
+
+// g2
+static int factor_effects(bool add, const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out,
+                          const double* factors, int k, int64_t ld_f, int64_t fs, const double* beta, int64_t ld_b,
+                          void* stream) {
+    const char* name = add ? "factor_add" : "factor_remove";
+    int r;
+    if ((r = factor_panel(factors, S, T, k, ld_f, fs, name))) return r;
+    if ((r = check_panel(in, S, T, ld_in, name))) return r;
+    if ((r = check_panel(out, S, T, ld_out, name))) return r;
+    if (ld_b < (int64_t)k + 1)
+        return fail(STS_ERR_BAD_ARG, "%s: coefficient leading dimension %lld < k + 1 = %d", name, (long long)ld_b, k + 1);
+    if (S > 0 && !beta) return fail(STS_ERR_BAD_ARG, "%s: null coefficient pointer", name);
+    if (S * T == 0) return STS_OK;
+    if (in == out && ld_in != ld_out) return fail(STS_ERR_BAD_ARG, "%s: in-place call with different ld", name);
+    if ((r = ensure_device())) return r;
+    HIP_TRY(sts::launch_factor_effects(add, in, out, S, T, ld_in, ld_out, factors, k, ld_f, fs, beta, ld_b,
+                                       as_stream(stream)), name);
+    return STS_OK;
+}
+
+int sts_factor_remove(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out,
+                      const double* factors, int k, int64_t ld_f, int64_t fs, const double* beta, int64_t ld_b,
+                      void* stream) {
+    return factor_effects(false, in, out, S, T, ld_in, ld_out, factors, k, ld_f, fs, beta, ld_b, stream);
+}
+
+int sts_factor_add(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out,
+                   const double* factors, int k, int64_t ld_f, int64_t fs, const double* beta, int64_t ld_b,
+                   void* stream) {
+    return factor_effects(true, in, out, S, T, ld_in, ld_out, factors, k, ld_f, fs, beta, ld_b, stream);
+}
+
 int sts_gen_panel(double* out, int64_t s0, int64_t S, int64_t T, int64_t ld, uint64_t seed, double nan_p,
                   void* stream) {
     int r;

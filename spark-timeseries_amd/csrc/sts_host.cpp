@@ -647,23 +647,20 @@ int sts_lb_test_host(const double* in, int64_t S, int64_t T, int64_t ld, int max
     });
 }
 
-// bgtest / bptest: a shared factor matrix (fs == 0) is copied to the device once, row by row (only
-// the T elements of each factor row are read), and every chunk of residuals runs against it;
-// per-series factors ride the staging pipeline as one block of (k - 1) * ld_f + T doubles per series
-// (the padding between a series' own factor rows is moved with it and never used).
-static int bgbp_host(bool bp, const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k,
-                     int64_t ld_f, int64_t fs, int max_lag, double* stat, double* pvalue, int32_t* err) {
-    auto dev_call = [&](const double* e, int64_t n, int64_t lde, const double* f, int64_t ldf, int64_t fsf, double* st,
-                        double* pv, int32_t* er, hipStream_t s) {
-        return bp ? sts_bp_test(e, n, T, lde, f, k, ldf, fsf, st, pv, er, s)
-                  : sts_bg_test(e, n, T, lde, f, k, ldf, fsf, max_lag, st, pv, er, s);
-    };
+// Calls with a factor panel (bgtest / bptest, include/sts_regress.h): a shared factor matrix
+// (fs == 0) is copied to the device once, row by row (only the T elements of each factor row are
+// read), and every chunk runs against it; per-series factors ride the staging pipeline as one block
+// of (k - 1) * ld_f + T doubles per series (the padding between a series' own factor rows is moved
+// with it and never used).  `call` is the wrapper's one device call, given the Call and the factor
+// panel to pass: (factors, ld_f, fs).
+using FactorCall = std::function<int(const Call&, const double*, int64_t, int64_t)>;
+static int staged_with_factors(int64_t S, int64_t T, int64_t ld, const double* factors, int k, int64_t ld_f,
+                               int64_t fs, std::vector<Arg> args, const FactorCall& call) {
     // a validation of this wrapper's own, ahead of staged()'s: the sizes below (k rows, the factor
     // span) must not overflow, and shared factors are uploaded before the pipeline runs -- nothing is
     // copied on bad input
     bool work = false;
-    const int r = sts::validate(
-        [&] { return dev_call(resid, S, ld, factors, ld_f, fs, stat, pvalue, nullptr, nullptr); }, &work);
+    const int r = sts::validate([&] { return call(Call{args, nullptr, S, ld, nullptr}, factors, ld_f, fs); }, &work);
     if (r || !work) return r;
     const size_t row = (size_t)T * sizeof(double);
     const int64_t span = (int64_t)(k - 1) * ld_f + T;
@@ -679,15 +676,25 @@ static int bgbp_host(bool bp, const double* resid, int64_t S, int64_t T, int64_t
     }
     // what the device call is given as factors: the uploaded copy (packed rows), or the chunk's own
     // blocks (during validation the caller's, at a stride the check above accepted)
-    const Arg own = fs == 0 ? Arg() : in_arg(factors, (size_t)span * sizeof(double), (size_t)fs * sizeof(double));
-    ErrOut eo(err, S);
-    const int st = staged(S, T, ld, {in_panel(resid), own, out_vec(stat), out_vec(pvalue), status(eo)},
-                          [&](const Call& c) {
-                              const double* f = fs == 0 ? static_cast<const double*>(df) : c.in(1);
-                              return dev_call(c.in(0), c.n, c.ld, f, fs == 0 ? T : ld_f, fs == 0 ? 0 : span, c.out(2),
-                                              c.out(3), c.err(4), c.st);
-                          });
+    const size_t own = args.size();
+    args.push_back(fs == 0 ? Arg() : in_arg(factors, (size_t)span * sizeof(double), (size_t)fs * sizeof(double)));
+    const int st = staged(S, T, ld, args, [&](const Call& c) {
+        const double* f = fs == 0 ? static_cast<const double*>(df) : c.in(own);
+        return call(c, f, fs == 0 ? T : ld_f, fs == 0 ? 0 : span);
+    });
     if (df) (void)hipFree(df);   // every chunk is back
+    return st;
+}
+
+static int bgbp_host(bool bp, const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k,
+                     int64_t ld_f, int64_t fs, int max_lag, double* stat, double* pvalue, int32_t* err) {
+    ErrOut eo(err, S);
+    const int st = staged_with_factors(
+        S, T, ld, factors, k, ld_f, fs, {in_panel(resid), out_vec(stat), out_vec(pvalue), status(eo)},
+        [&](const Call& c, const double* f, int64_t ldf, int64_t fsf) {
+            return bp ? sts_bp_test(c.in(0), c.n, T, c.ld, f, k, ldf, fsf, c.out(1), c.out(2), c.err(3), c.st)
+                      : sts_bg_test(c.in(0), c.n, T, c.ld, f, k, ldf, fsf, max_lag, c.out(1), c.out(2), c.err(3), c.st);
+        });
     return eo.finish(st, S, bp ? "bptest" : "bgtest");
 }
 
@@ -699,6 +706,42 @@ int sts_bp_test_host(const double* resid, int64_t S, int64_t T, int64_t ld, cons
 int sts_bg_test_host(const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k, int64_t ld_f,
                      int64_t fs, int max_lag, double* stat, double* pvalue, int32_t* err) {
     return bgbp_host(false, resid, S, T, ld, factors, k, ld_f, fs, max_lag, stat, pvalue, err);
+}
+
+// ---- include/sts_regress.h: beta and stderr packed (k + 1 wide, 0 for a k the entry point rejects),
+// the residual panel at the input's ld ----
+
+int sts_factor_ols_host(const double* y, int64_t S, int64_t T, int64_t ld, const double* factors, int k, int64_t ld_f,
+                        int64_t fs, double* beta, double* stderr_out, double* stats, double* resid, int32_t* err) {
+    const int64_t w = (k >= 1 && k <= STS_MAX_FACTORS) ? k + 1 : 0;
+    ErrOut eo(err, S);
+    const int st = staged_with_factors(
+        S, T, ld, factors, k, ld_f, fs,
+        {in_panel(y), out_vec(beta, w), out_vec(stderr_out, w), out_vec(stats, 4), out_panel(resid), status(eo)},
+        [&](const Call& c, const double* f, int64_t ldf, int64_t fsf) {
+            return sts_factor_ols(c.in(0), c.n, T, c.ld, f, k, ldf, fsf, c.out(1), k + 1, c.out(2), c.out(3), c.out(4),
+                                  c.ld, c.err(5), c.st);
+        });
+    return eo.finish(st, S, "factor_ols");
+}
+
+static int factor_effects_host(decltype(&sts_factor_add) fn, const double* in, double* out, int64_t S, int64_t T,
+                               int64_t ld, const double* factors, int k, int64_t ld_f, int64_t fs, const double* beta) {
+    const int64_t w = (k >= 1 && k <= STS_MAX_FACTORS) ? k + 1 : 0;
+    return staged_with_factors(S, T, ld, factors, k, ld_f, fs, {in_panel(in), out_panel(out), in_vec(beta, w)},
+                               [&](const Call& c, const double* f, int64_t ldf, int64_t fsf) {
+                                   return fn(c.in(0), c.out(1), c.n, T, c.ld, c.ld, f, k, ldf, fsf, c.in(2), k + 1, c.st);
+                               });
+}
+
+int sts_factor_remove_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, const double* factors, int k,
+                           int64_t ld_f, int64_t fs, const double* beta) {
+    return factor_effects_host(sts_factor_remove, in, out, S, T, ld, factors, k, ld_f, fs, beta);
+}
+
+int sts_factor_add_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, const double* factors, int k,
+                        int64_t ld_f, int64_t fs, const double* beta) {
+    return factor_effects_host(sts_factor_add, in, out, S, T, ld, factors, k, ld_f, fs, beta);
 }
 
 // ---- panel transforms (include/sts_transforms.h).  An output of another width than the input is

@@ -10,6 +10,7 @@
 #include "sts_transforms.h"
 #include "sts_sample.h"
 #include "sts_index.h"
+#include "sts_regress.h"
 
 namespace sts {
 
@@ -348,6 +349,43 @@ hipError_t launch_factor_basis(const BgBpArgs& a, int64_t s0, int64_t nb, hipStr
 // statistics of series s0 .. s0 + ns; basis / info are indexed from the chunk's first series
 hipError_t launch_bgbp(const BgBpArgs& a, int64_t s0, int64_t ns, hipStream_t st);
 hipError_t launch_chi2_pvalue(const double* stat, double* pv, int64_t S, int dof, hipStream_t st);
+// A remainder of at most this share of the centred column counts as none: twice-applied
+// Gram-Schmidt leaves rounding noise of a few ulps of the column where exact arithmetic leaves 0
+// (a duplicated factor), and a factor collinear to 1e-6 leaves a million times the bound.
+constexpr double kBasisTol2 = 0x1p-80;   // (2^-40)^2, on squared norms
+
+// OLS of a panel on factors and the effects pair (sts_regress.hip, include/sts_regress.h)
+struct OlsArgs {
+    const double* y;
+    int64_t S, T, ld;
+    const double* factors;   // as BgBpArgs
+    int64_t ld_f, fs;
+    int k;
+    double* basis;           // scratch: k x T per basis, basis b at basis + b * basis_stride
+    int64_t basis_stride;    // 0: one basis for every series
+    double* aux;             // scratch: kOlsAux doubles per basis (R^-1, factor means, ...), b * aux_stride
+    int64_t aux_stride;      // 0 or kOlsAux
+    double* beta;            // S x (k + 1) at ld_b
+    double* se;              // optional, as beta
+    int64_t ld_b;
+    double* stats;           // optional, S x 4: rss, tss, r2, sigma2
+    double* resid;           // optional, S x T at ld_r
+    int64_t ld_r;
+    int32_t* err;            // per-series status, zeroed by the caller
+};
+constexpr int kOlsAux = 152;
+// which of launch_ols's kernels a call takes (tests name the seams): 0 = shared factors, several
+// waves per workgroup with the basis staged in LDS; 1 = one wave per series, basis in the scratch;
+// 2 = one wave per series that builds its own factors' basis in LDS (no scratch); 3 = 256-thread
+// sweeps over global memory
+int ols_regime(int64_t T, int k, int64_t fs);
+// bases (with R^-1 and the means) of series s0 .. s0 + nb into a.basis / a.aux; a no-op in regime 2
+hipError_t launch_ols_basis(const OlsArgs& a, int64_t s0, int64_t nb, hipStream_t st);
+// fits of series s0 .. s0 + ns; basis / aux are indexed from the chunk's first series
+hipError_t launch_ols(const OlsArgs& a, int64_t s0, int64_t ns, hipStream_t st);
+hipError_t launch_factor_effects(bool add, const double* in, double* out, int64_t S, int64_t T, int64_t ld_in,
+                                 int64_t ld_out, const double* factors, int k, int64_t ld_f, int64_t fs,
+                                 const double* beta, int64_t ld_b, hipStream_t st);
 
 // seriesStats / removeInstantsWithNaNs / toInstants (sts_instants.hip)
 hipError_t launch_series_stats(const double* in, double* out, int64_t S, int64_t T, int64_t ld, hipStream_t st);

@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "sts_internal.hpp"
+#include "sts_wgsum.hpp"
 
 namespace sts {
 namespace {
@@ -29,52 +30,7 @@ namespace {
 constexpr int kLongThreads = 256;
 constexpr int kMaxCols = 33;   // ADF: 31 lags + level + response
 
-// ---- workgroup-wide sum / inclusive scan (NT = 64: one wave, shuffles only) ----
-// Every thread gets the same bits (a butterfly of commutative additions), so branches on a
-// reduced value are uniform.
-template <int NT>
-__device__ __forceinline__ double bsum(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-    if constexpr (NT > 64) {
-        __syncthreads();   // red[] free again
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        v = red[0];
-#pragma unroll
-        for (int i = 1; i < NT / 64; i++) v += red[i];
-    }
-    return v;
-}
-
-// The first `live` (uniform) of N sums at once: their butterflies interleave, so a wave waits for
-// one chain of shuffles, not `live` of them (red: N x 4 doubles when NT > 64)
-template <int NT, int N>
-__device__ __forceinline__ void bsum_many(double (&v)[N], int live, double* red) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1)
-#pragma unroll
-        for (int c = 0; c < N; c++)
-            if (c < live) v[c] += __shfl_xor(v[c], o, 64);
-    if constexpr (NT > 64) {
-        __syncthreads();   // red[] free again
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int c = 0; c < N; c++)
-                if (c < live) red[c * 4 + (threadIdx.x >> 6)] = v[c];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < N; c++)
-            if (c < live) {
-                double t = red[c * 4];
-#pragma unroll
-                for (int i = 1; i < NT / 64; i++) t += red[c * 4 + i];
-                v[c] = t;
-            }
-    }
-}
-
+// ---- workgroup-wide inclusive scan (the sums: sts_wgsum.hpp) ----
 template <int NT>
 __device__ __forceinline__ double bscan(double v, double* red, double& total) {
     const int lane = threadIdx.x & 63;
@@ -520,11 +476,6 @@ __global__ void lb_kernel(const double* __restrict__ acf, int64_t S, int64_t T, 
 // the response treated alike and Lz the Cholesky factor of the lags' Gram matrix Z'Z alone (as
 // adf_kernel).  No term is a difference of large numbers, so R^2 keeps its relative accuracy
 // where 1 - RSS / TSS and a pivot of the whole Gram matrix lose theirs.
-
-// A remainder of at most this share of the centred column counts as none: twice-applied
-// Gram-Schmidt leaves rounding noise of a few ulps of the column where exact arithmetic leaves 0
-// (a duplicated factor), and a factor collinear to 1e-6 leaves a million times the bound.
-constexpr double kBasisTol2 = 0x1p-80;   // (2^-40)^2, on squared norms
 
 // The orthonormal basis of one factor matrix: Q (k x n, row c at Q + c * n; global scratch or LDS),
 // from rows 0..n of the k factor rows at F; true when the factors are rank deficient.  Each thread

@@ -1,5 +1,5 @@
 """Loader and ctypes bindings for libsts_hip.so (the C ABI in include/sts.h, include/sts_transforms.h,
-include/sts_sample.h and include/sts_index.h).
+include/sts_sample.h, include/sts_index.h and include/sts_regress.h).
 
 This is the Python analogue of the JNI shim: plain pointers and
 sizes cross the boundary, no torch types.  There is deliberately NO fallback:
@@ -176,9 +176,22 @@ INDEX_SIGNATURES = {
 }
 INDEX_DAYS, INDEX_HOURS, INDEX_BUSINESS_DAYS, INDEX_IRREGULAR = 0, 1, 2, 3
 
+# OLS of a panel on factors and the effects pair, include/sts_regress.h, the fifth sibling header
+# (tests/test_factor_ols_cpu.py holds this table to it).  A factor panel travels as factors, k, ld_f, fs.
+_FACTORS = [_c_vp, _c_int, _c_i64, _c_i64]
+REGRESS_SIGNATURES = {
+    "sts_factor_ols": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64] + _FACTORS + [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64,
+                                                                              _c_vp, _c_vp]),
+    "sts_factor_remove": (_c_int, _PANELS + _FACTORS + [_c_vp, _c_i64, _c_vp]),
+    "sts_factor_add": (_c_int, _PANELS + _FACTORS + [_c_vp, _c_i64, _c_vp]),
+    "sts_factor_ols_host": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64] + _FACTORS + [_c_vp] * 5),
+    "sts_factor_remove_host": (_c_int, _PANELS_HOST + _FACTORS + [_c_vp]),
+    "sts_factor_add_host": (_c_int, _PANELS_HOST + _FACTORS + [_c_vp]),
+}
+
 
 def _bind(handle):
-    for table in (SIGNATURES, TRANSFORM_SIGNATURES, SAMPLE_SIGNATURES, INDEX_SIGNATURES):
+    for table in (SIGNATURES, TRANSFORM_SIGNATURES, SAMPLE_SIGNATURES, INDEX_SIGNATURES, REGRESS_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(handle, name)
             fn.restype = res

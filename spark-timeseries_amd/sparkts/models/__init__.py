@@ -4,3 +4,4 @@ from .EWMA import EWMA, EWMAModel  # noqa: F401
 from .TimeSeriesModel import TimeSeriesModel  # noqa: F401
 from .ARIMA import ARIMA, ARIMAModel  # noqa: F401
 from .GARCH import ARGARCH, ARGARCHModel, GARCH, GARCHModel  # noqa: F401
+from .FactorRegression import FactorRegression, FactorRegressionModel  # noqa: F401

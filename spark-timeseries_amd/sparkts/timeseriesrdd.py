@@ -232,6 +232,16 @@ class TimeSeriesRDD:
         from .stats import factor_tests
         return factor_tests.bptest(self.data, factors)
 
+    def regress(self, factors, residuals: bool = True):
+        """rdd.mapValues(OLS with intercept on the factors) in one batched call: the OLSResult of
+        stats.ols, its residuals a TimeSeriesRDD with this one's keys and index, so
+        rdd.regress(F).residuals.bgtest(F, 5) never leaves the device."""
+        from .stats import regression
+        r = regression.ols(self.data, factors, residuals)
+        if r.residuals is not None:
+            r.residuals = self._derive(r.residuals)
+        return r
+
     def fillAndAutocorr(self, method: str, numLags: int):
         """fill(method) followed by autocorr of every filled series, fused into one pass
         over HBM.  Returns (filled TimeSeriesRDD, acf (S, K))."""
