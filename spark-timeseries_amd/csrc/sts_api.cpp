@@ -1850,6 +1850,64 @@ int sts_factor_add(const double* in, double* out, int64_t S, int64_t T, int64_t 
     return factor_effects(true, in, out, S, T, ld_in, ld_out, factors, k, ld_f, fs, beta, ld_b, stream);
 }
 
+// ---- include/sts_cross.h ----
+
+int sts_cross_kind_from_name(const char* name) {
+    if (!name) return -2;
+    if (!std::strcmp(name, "cov")) return STS_CROSS_COV;
+    if (!std::strcmp(name, "corr")) return STS_CROSS_CORR;
+    return -2;
+}
+
+// do the S x w block at a (rows ld apart) and the S_b x w_b block at b share a byte?  Extents only:
+// a block is taken as the one range from its first to its last element.
+static bool blocks_overlap(const double* a, int64_t S, int64_t ld, int64_t w, const double* b, int64_t S_b, int64_t ld_b,
+                           int64_t w_b) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    const uintptr_t a1 = a0 + ((uintptr_t)(S - 1) * (uintptr_t)ld + (uintptr_t)w) * sizeof(double);
+    const uintptr_t b1 = b0 + ((uintptr_t)(S_b - 1) * (uintptr_t)ld_b + (uintptr_t)w_b) * sizeof(double);
+    return a0 < b1 && b0 < a1;
+}
+
+// c1.  Scratch: kCrossStat doubles per series of either panel, and in a split plan (cross_plan) the
+// (tile, segment) partials.
+int sts_cross_moments(const double* x, int64_t Sx, int64_t T, int64_t ld_x, const double* y, int64_t Sy, int64_t ld_y,
+                      int kind, double* out, int64_t ld_o, double* mean_x, double* mean_y, void* stream) {
+    const char* name = "cross_moments";
+    if (!x || !out) return fail(STS_ERR_BAD_ARG, "%s: null %s pointer", name, !x ? "panel" : "output");
+    if (Sx < 1) return fail(STS_ERR_BAD_ARG, "%s: Sx=%lld < 1", name, (long long)Sx);
+    if (y && Sy < 1) return fail(STS_ERR_BAD_ARG, "%s: Sy=%lld < 1", name, (long long)Sy);
+    if (T < 0 || T > 0x7fffffffLL)
+        return fail(STS_ERR_BAD_ARG, "%s: T=%lld outside the reference's Int index range", name, (long long)T);
+    if (ld_x < T) return fail(STS_ERR_BAD_ARG, "%s: leading dimension %lld < T=%lld", name, (long long)ld_x, (long long)T);
+    if (y && ld_y < T)
+        return fail(STS_ERR_BAD_ARG, "%s: leading dimension of y %lld < T=%lld", name, (long long)ld_y, (long long)T);
+    const int64_t cols = y ? Sy : Sx;
+    if (ld_o < cols)
+        return fail(STS_ERR_BAD_ARG, "%s: output leading dimension %lld < %lld columns", name, (long long)ld_o,
+                    (long long)cols);
+    if (kind != STS_CROSS_COV && kind != STS_CROSS_CORR) return fail(STS_ERR_BAD_ARG, "%s: kind %d is not cov or corr", name, kind);
+    if (mean_y && !y) return fail(STS_ERR_BAD_ARG, "%s: mean_y without y", name);
+    const int64_t w = T > 0 ? T : 1;
+    if (blocks_overlap(out, Sx, ld_o, cols, x, Sx, ld_x, w) || (y && blocks_overlap(out, Sx, ld_o, cols, y, Sy, ld_y, w)))
+        return fail(STS_ERR_BAD_ARG, "%s: out overlaps an input panel", name);
+    if (T < 2) return fail(STS_ERR_NOT_ENOUGH_DATA, "%s: %lld instants, a covariance needs 2", name, (long long)T);
+    const sts::CrossPlan plan = sts::cross_plan(Sx, cols, T, y == nullptr);
+    if (plan.tiles > 0x7fffffffLL)
+        return fail(STS_ERR_BAD_ARG, "%s: %lld x %lld outputs exceed one launch", name, (long long)Sx, (long long)cols);
+    int r;
+    if ((r = ensure_device())) return r;
+    hipStream_t st = as_stream(stream);
+    Scratch sc(st);
+    HIP_TRY(sc.alloc(plan.scratch_doubles * sizeof(double)), "hipMallocAsync(cross scratch)");
+    sts::CrossArgs a{};
+    a.x = x; a.y = y; a.Sx = Sx; a.Sy = cols; a.T = T; a.ld_x = ld_x; a.ld_y = y ? ld_y : ld_x; a.kind = kind;
+    a.out = out; a.ld_o = ld_o; a.mean_x = mean_x; a.mean_y = mean_y;
+    a.scratch = static_cast<double*>(sc.p);
+    HIP_TRY(timed(st, [&] { return sts::launch_cross(a, st); }), name);
+    return STS_OK;
+}
+
 int sts_gen_panel(double* out, int64_t s0, int64_t S, int64_t T, int64_t ld, uint64_t seed, double nan_p,
                   void* stream) {
     int r;

@@ -744,6 +744,48 @@ int sts_factor_add_host(const double* in, double* out, int64_t S, int64_t T, int
     return factor_effects_host(sts_factor_add, in, out, S, T, ld, factors, k, ld_f, fs, beta);
 }
 
+// ---- include/sts_cross.h.  Every output depends on two series that may lie anywhere in the two
+// panels, so there are no chunks of series to pipeline: both panels are copied to the device whole
+// (packed rows, only the T elements of a row are read), the one device call runs on the calling
+// thread's stream, and the packed matrix and the means come back.  `call` is the wrapper's one device
+// call: first in validate-only mode on the caller's pointers and ld, then on the device copies. ----
+
+int sts_cross_moments_host(const double* x, int64_t Sx, int64_t T, int64_t ld_x, const double* y, int64_t Sy, int64_t ld_y,
+                           int kind, double* out, double* mean_x, double* mean_y) {
+    const int64_t cols = y ? Sy : Sx;
+    const auto call = [&](const double* px, int64_t ldx, const double* py, int64_t ldy, double* po, double* mx, double* my) {
+        return sts_cross_moments(px, Sx, T, ldx, py, Sy, ldy, kind, po, cols, mx, my, nullptr);
+    };
+    bool work = false;
+    const int r = sts::validate([&] { return call(x, ld_x, y, ld_y, out, mean_x, mean_y); }, &work);
+    if (r || !work) return r;
+    const size_t row = (size_t)T * sizeof(double);
+    const size_t nx = (size_t)Sx * (size_t)T, ny = y ? (size_t)Sy * (size_t)T : 0, no = (size_t)Sx * (size_t)cols;
+    struct Dev {
+        void* p = nullptr;
+        ~Dev() {
+            if (p) (void)hipFree(p);
+        }
+    } dev;
+    hipError_t e = hipMalloc(&dev.p, (nx + ny + no + (size_t)Sx + (size_t)cols) * sizeof(double));
+    if (e != hipSuccess) return hip_status(e, "hipMalloc(cross_moments)");
+    double* dx = static_cast<double*>(dev.p);
+    double* dy = y ? dx + nx : nullptr;
+    double* dout = dx + nx + ny;
+    double* dmx = mean_x ? dout + no : nullptr;
+    double* dmy = mean_y ? dout + no + Sx : nullptr;
+    e = hipMemcpy2D(dx, row, x, (size_t)ld_x * sizeof(double), row, (size_t)Sx, hipMemcpyHostToDevice);
+    if (e == hipSuccess && y) e = hipMemcpy2D(dy, row, y, (size_t)ld_y * sizeof(double), row, (size_t)Sy, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_status(e, "hipMemcpy2D(cross_moments)");
+    const int st = call(dx, T, dy, T, dout, dmx, dmy);
+    e = hipStreamSynchronize(hipStreamPerThread);   // also on a failed call: nothing of it may outlive the buffer
+    if (st != STS_OK) return st;
+    if (e == hipSuccess) e = hipMemcpy(out, dout, no * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && mean_x) e = hipMemcpy(mean_x, dmx, (size_t)Sx * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && mean_y) e = hipMemcpy(mean_y, dmy, (size_t)cols * sizeof(double), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? STS_OK : hip_status(e, "cross_moments (host)");
+}
+
 // ---- panel transforms (include/sts_transforms.h).  An output of another width than the input is
 // packed (out_vec): the width is computed here, for the staging size alone and only for a shape the
 // device entry point accepts (so it cannot overflow); every other shape gets width 0 and the entry

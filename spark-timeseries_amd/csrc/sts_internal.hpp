@@ -11,6 +11,7 @@
 #include "sts_sample.h"
 #include "sts_index.h"
 #include "sts_regress.h"
+#include "sts_cross.h"
 
 namespace sts {
 
@@ -386,6 +387,33 @@ hipError_t launch_ols(const OlsArgs& a, int64_t s0, int64_t ns, hipStream_t st);
 hipError_t launch_factor_effects(bool add, const double* in, double* out, int64_t S, int64_t T, int64_t ld_in,
                                  int64_t ld_out, const double* factors, int k, int64_t ld_f, int64_t fs,
                                  const double* beta, int64_t ld_b, hipStream_t st);
+
+// covariance / correlation matrices (sts_cross.hip, include/sts_cross.h)
+constexpr int kCrossTile = STS_CROSS_TILE;     // output tile of one workgroup, square
+constexpr int kCrossChunk = STS_CROSS_CHUNK;   // steps of T per LDS stage
+constexpr int64_t kCrossSplit = STS_CROSS_SPLIT;   // steps after which a partial sum over T is closed
+constexpr int kCrossStat = 4;                  // per series in the scratch: mu, r, C_ii, flag (0 / 1 constant / 2 non-finite)
+struct CrossArgs {
+    const double* x;
+    const double* y;         // null: the symmetric form
+    int64_t Sx, Sy, T, ld_x, ld_y;
+    int kind;
+    double* out;
+    int64_t ld_o;
+    double* mean_x;          // optional
+    double* mean_y;
+    double* scratch;         // cross_plan().scratch_doubles doubles
+};
+// what a call launches: the tile grid, the segments of T (closed every kCrossSplit steps) and whether
+// each segment gets a workgroup of its own (few tiles, long T) with a finalise kernel behind them
+struct CrossPlan {
+    int64_t ti, tj, tiles, nseg;
+    bool split;
+    size_t scratch_doubles;
+};
+CrossPlan cross_plan(int64_t Sx, int64_t Sy, int64_t T, bool symmetric);
+// the prep kernel(s), the Gram kernel and, in a split plan, the finalise kernel
+hipError_t launch_cross(const CrossArgs& a, hipStream_t st);
 
 // seriesStats / removeInstantsWithNaNs / toInstants (sts_instants.hip)
 hipError_t launch_series_stats(const double* in, double* out, int64_t S, int64_t T, int64_t ld, hipStream_t st);

@@ -1,5 +1,5 @@
 """Loader and ctypes bindings for libsts_hip.so (the C ABI in include/sts.h, include/sts_transforms.h,
-include/sts_sample.h, include/sts_index.h and include/sts_regress.h).
+include/sts_sample.h, include/sts_index.h, include/sts_regress.h and include/sts_cross.h).
 
 This is the Python analogue of the JNI shim: plain pointers and
 sizes cross the boundary, no torch types.  There is deliberately NO fallback:
@@ -189,9 +189,20 @@ REGRESS_SIGNATURES = {
     "sts_factor_add_host": (_c_int, _PANELS_HOST + _FACTORS + [_c_vp]),
 }
 
+# Covariance and correlation matrices, include/sts_cross.h, the sixth sibling header
+# (tests/test_cross_cpu.py holds this table to it): x, Sx, T, ld_x, then y, Sy, ld_y, then kind.
+_TWO_PANELS = [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_i64, _c_int]
+CROSS_SIGNATURES = {
+    "sts_cross_kind_from_name": (_c_int, [ctypes.c_char_p]),
+    "sts_cross_moments": (_c_int, _TWO_PANELS + [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp]),
+    "sts_cross_moments_host": (_c_int, _TWO_PANELS + [_c_vp, _c_vp, _c_vp]),
+}
+CROSS_COV, CROSS_CORR = 0, 1
+
 
 def _bind(handle):
-    for table in (SIGNATURES, TRANSFORM_SIGNATURES, SAMPLE_SIGNATURES, INDEX_SIGNATURES, REGRESS_SIGNATURES):
+    for table in (SIGNATURES, TRANSFORM_SIGNATURES, SAMPLE_SIGNATURES, INDEX_SIGNATURES, REGRESS_SIGNATURES,
+                  CROSS_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(handle, name)
             fn.restype = res

@@ -1,8 +1,9 @@
 """com.cloudera.sparkts.stats: batched statistical tests over series and panels."""
-from . import TimeSeriesStatisticalTests, factor_tests, regression
+from . import TimeSeriesStatisticalTests, cross, factor_tests, regression
 from .TimeSeriesStatisticalTests import adftest, dwtest, kpsstest, lbtest
+from .cross import corr, cov
 from .factor_tests import bgtest, bptest
 from .regression import OLSResult, ols
 
-__all__ = ["TimeSeriesStatisticalTests", "factor_tests", "regression", "adftest", "bgtest", "bptest", "dwtest", "kpsstest",
-           "lbtest", "ols", "OLSResult"]
+__all__ = ["TimeSeriesStatisticalTests", "cross", "factor_tests", "regression", "adftest", "bgtest", "bptest", "corr", "cov",
+           "dwtest", "kpsstest", "lbtest", "ols", "OLSResult"]

@@ -242,6 +242,40 @@ class TimeSeriesRDD:
             r.residuals = self._derive(r.residuals)
         return r
 
+    def _cross_other(self, other, name):
+        """`other` of covariance / correlation as a panel with this one's instants: another
+        TimeSeriesRDD's panel, or the columns of a (T, k) factor matrix as regress takes it (a view:
+        a Breeze DenseMatrix(T, k)'s data is a k-series panel with ld = T)."""
+        from .errors import IllegalArgumentException
+        if other is None:
+            return None
+        T = int(self.data.shape[-1])
+        if isinstance(other, TimeSeriesRDD):
+            if int(other.data.shape[-1]) != T:
+                raise IllegalArgumentException("%s: the other RDD has %d instants, this one %d"
+                                               % (name, int(other.data.shape[-1]), T))
+            if _is_datetime_index(self.index) and _is_datetime_index(other.index) and self.index != other.index:
+                raise IllegalArgumentException("%s: the two RDDs have different date-time indices" % name)
+            return other.data
+        shape = tuple(int(v) for v in getattr(other, "shape", ()))
+        if len(shape) != 2 or shape[0] != T or shape[1] < 1:
+            raise IllegalArgumentException("%s: other must be a TimeSeriesRDD or a (T, k) factor matrix with T=%d, got "
+                                           "shape %s" % (name, T, shape))
+        return other.transpose(0, 1) if hasattr(other, "stride") else other.T
+
+    def covariance(self, other=None):
+        """toRowMatrix().computeCovariance() of the reference's users, on the series-major panel in
+        one call: the (S, S) sample covariance matrix of this RDD's series, rows and columns in
+        `keys` order; with `other` (a TimeSeriesRDD on the same instants, or a (T, k) factor matrix)
+        the (S, S') / (S, k) matrix of this RDD's series against the other's."""
+        from .stats import cross
+        return cross.cov(self.data, self._cross_other(other, "covariance"))
+
+    def correlation(self, other=None):
+        """Statistics.corr on the instants: Pearson correlations, as covariance()."""
+        from .stats import cross
+        return cross.corr(self.data, self._cross_other(other, "correlation"))
+
     def fillAndAutocorr(self, method: str, numLags: int):
         """fill(method) followed by autocorr of every filled series, fused into one pass
         over HBM.  Returns (filled TimeSeriesRDD, acf (S, K))."""
