@@ -1908,6 +1908,69 @@ int sts_cross_moments(const double* x, int64_t Sx, int64_t T, int64_t ld_x, cons
     return STS_OK;
 }
 
+// ---- include/sts_roll.h ----
+
+int sts_roll_op_from_name(const char* name) {
+    static const char* const names[] = {"sum", "mean", "var", "std", "min", "max", "zscore"};
+    if (!name) return -2;
+    for (int i = 0; i < 7; i++)
+        if (!std::strcmp(name, names[i])) return i;
+    return -2;
+}
+
+int sts_roll_pair_op_from_name(const char* name) {
+    static const char* const names[] = {"cov", "corr", "beta"};
+    if (!name) return -2;
+    for (int i = 0; i < 3; i++)
+        if (!std::strcmp(name, names[i])) return i;
+    return -2;
+}
+
+// r1 / r2: the guards both share, in the header's order; y == nullptr for r1.  No scratch: every
+// launch reads the inputs and writes out.
+static int roll_call(const char* name, const double* x, const double* y, int64_t Sy, int64_t ld_y, double* out, int64_t S,
+                     int64_t T, int64_t ld_x, int64_t ld_out, int window, int min_periods, int op, bool pair, void* stream) {
+    if (!x || !out || (pair && !y))
+        return fail(STS_ERR_BAD_ARG, "%s: null %s pointer", name, !x ? "panel" : !out ? "output" : "y");
+    if (S < 1 || T < 1) return fail(STS_ERR_BAD_ARG, "%s: empty panel (S=%lld, T=%lld)", name, (long long)S, (long long)T);
+    if (T > 0x7fffffffLL)
+        return fail(STS_ERR_BAD_ARG, "%s: T=%lld exceeds the reference's Int index range", name, (long long)T);
+    if (ld_x < T || ld_out < T)
+        return fail(STS_ERR_BAD_ARG, "%s: leading dimension %lld < T=%lld", name, (long long)(ld_x < T ? ld_x : ld_out),
+                    (long long)T);
+    if (window < 1 || window > STS_ROLL_MAX_WINDOW)
+        return fail(STS_ERR_BAD_ARG, "%s: window %d outside [1, %d]", name, window, STS_ROLL_MAX_WINDOW);
+    if (min_periods < 1 || min_periods > window)
+        return fail(STS_ERR_BAD_ARG, "%s: min_periods %d outside [1, window=%d]", name, min_periods, window);
+    if (op < 0 || op > (pair ? (int)STS_ROLL_BETA : (int)STS_ROLL_ZSCORE))
+        return fail(STS_ERR_BAD_ARG, "%s: op %d is not one of the header's", name, op);
+    if (pair) {
+        if (Sy != 1 && Sy != S) return fail(STS_ERR_BAD_ARG, "%s: Sy=%lld is neither 1 nor S=%lld", name, (long long)Sy, (long long)S);
+        if (Sy != 1 && ld_y < T)
+            return fail(STS_ERR_BAD_ARG, "%s: leading dimension of y %lld < T=%lld", name, (long long)ld_y, (long long)T);
+    }
+    if (blocks_overlap(out, S, ld_out, T, x, S, ld_x, T) ||
+        (pair && blocks_overlap(out, S, ld_out, T, y, Sy, Sy == 1 ? T : ld_y, T)))
+        return fail(STS_ERR_BAD_ARG, "%s: out overlaps an input panel", name);
+    int r;
+    if ((r = ensure_device())) return r;
+    sts::RollArgs a{};
+    a.x = x; a.y = y; a.out = out; a.S = S; a.T = T; a.ld_x = ld_x; a.ld_y = pair && Sy != 1 ? ld_y : 0; a.ld_out = ld_out;
+    a.window = window; a.min_periods = min_periods; a.op = op; a.pair = pair;
+    HIP_TRY(sts::launch_roll(a, as_stream(stream)), name);
+    return STS_OK;
+}
+
+int sts_roll_stat(const double* in, double* out, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, int window,
+                  int min_periods, int op, void* stream) {
+    return roll_call("roll_stat", in, nullptr, 0, 0, out, S, T, ld_in, ld_out, window, min_periods, op, false, stream);
+}
+
+int sts_roll_pair(const double* x, const double* y, int64_t Sy, int64_t ld_y, double* out, int64_t S, int64_t T,
+                  int64_t ld_x, int64_t ld_out, int window, int min_periods, int op, void* stream) {
+    return roll_call("roll_pair", x, y, Sy, ld_y, out, S, T, ld_x, ld_out, window, min_periods, op, true, stream);
+}
+
 int sts_gen_panel(double* out, int64_t s0, int64_t S, int64_t T, int64_t ld, uint64_t seed, double nan_p,
                   void* stream) {
     int r;

@@ -786,6 +786,53 @@ int sts_cross_moments_host(const double* x, int64_t Sx, int64_t T, int64_t ld_x,
     return e == hipSuccess ? STS_OK : hip_status(e, "cross_moments (host)");
 }
 
+// ---- include/sts_roll.h.  An output depends on its own row alone, so the panels ride the staging
+// pipeline by chunks of series.  A per-series y is a third per-series array (T doubles per series,
+// ld_y apart on the host); a shared factor is uploaded once, outside the pipeline, as bgbp_host's
+// shared factors are. ----
+
+int sts_roll_stat_host(const double* in, double* out, int64_t S, int64_t T, int64_t ld, int window, int min_periods,
+                       int op) {
+    return staged(S, T, ld, {in_panel(in), out_panel(out)}, [&](const Call& c) {
+        return sts_roll_stat(c.in(0), c.out(1), c.n, T, c.ld, c.ld, window, min_periods, op, c.st);
+    });
+}
+
+int sts_roll_pair_host(const double* x, const double* y, int64_t Sy, int64_t ld_y, double* out, int64_t S, int64_t T,
+                       int64_t ld, int window, int min_periods, int op) {
+    const bool shared = Sy == 1;
+    // the device call on the caller's pointers: the chunk's Sy is its own series count, or 1
+    const auto call = [&](const double* px, const double* py, int64_t ldy, double* po, int64_t n, int64_t ldx, hipStream_t st,
+                          bool whole) {
+        return sts_roll_pair(px, py, whole ? Sy : (shared ? 1 : n), ldy, po, n, T, ldx, ldx, window, min_periods, op, st);
+    };
+    bool work = false;
+    const int r = sts::validate([&] { return call(x, y, ld_y, out, S, ld, nullptr, true); }, &work);
+    if (r || !work) return r;
+    const size_t row = (size_t)T * sizeof(double);
+    if (!shared) {
+        return staged(S, T, ld, {in_panel(x), out_panel(out), in_arg(y, row, (size_t)ld_y * sizeof(double))},
+                      [&](const Call& c) {
+                          const bool val = c.st == nullptr;   // staged()'s own validation: the caller's pointers
+                          return call(c.in(0), c.in(2), val ? ld_y : T, c.out(1), c.n, c.ld, c.st, val);
+                      });
+    }
+    void* df = nullptr;
+    hipError_t e = hipMalloc(&df, row);
+    if (e != hipSuccess) return hip_status(e, "hipMalloc(roll factor)");
+    e = hipMemcpy(df, y, row, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(df);
+        return hip_status(e, "hipMemcpy(roll factor)");
+    }
+    const int st = staged(S, T, ld, {in_panel(x), out_panel(out)}, [&](const Call& c) {
+        const bool val = c.st == nullptr;
+        return call(c.in(0), val ? y : static_cast<const double*>(df), T, c.out(1), c.n, c.ld, c.st, val);
+    });
+    (void)hipFree(df);   // every chunk is back
+    return st;
+}
+
 // ---- panel transforms (include/sts_transforms.h).  An output of another width than the input is
 // packed (out_vec): the width is computed here, for the staging size alone and only for a shape the
 // device entry point accepts (so it cannot overflow); every other shape gets width 0 and the entry

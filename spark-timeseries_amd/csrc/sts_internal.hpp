@@ -12,6 +12,7 @@
 #include "sts_index.h"
 #include "sts_regress.h"
 #include "sts_cross.h"
+#include "sts_roll.h"
 
 namespace sts {
 
@@ -414,6 +415,27 @@ struct CrossPlan {
 CrossPlan cross_plan(int64_t Sx, int64_t Sy, int64_t T, bool symmetric);
 // the prep kernel(s), the Gram kernel and, in a split plan, the finalise kernel
 hipError_t launch_cross(const CrossArgs& a, hipStream_t st);
+
+// rolling-window statistics (sts_roll.hip, include/sts_roll.h)
+constexpr int kRollTile = STS_ROLL_TILE;       // steps of one row a workgroup owns
+constexpr int kRollChains = STS_ROLL_CHAINS;   // outputs a thread carries at a time
+constexpr int kRollCap = kRollTile + STS_ROLL_MAX_WINDOW - 1;   // doubles of one LDS buffer: a tile and its halo
+struct RollArgs {
+    const double* x;
+    const double* y;         // pair ops only; ld_y == 0: one shared factor
+    double* out;
+    int64_t S, T, ld_x, ld_y, ld_out;
+    int window, min_periods, op;
+    bool pair;               // op is an sts_roll_pair_op
+};
+// a workgroup owns rows whole rows when T <= kRollTile (rows * (T + window - 1) <= kRollCap), else one
+// tile of one row; tiles = tiles per row
+struct RollPlan {
+    int64_t tiles;
+    int rows;
+};
+RollPlan roll_plan(int64_t T, int window);
+hipError_t launch_roll(const RollArgs& a, hipStream_t st);
 
 // seriesStats / removeInstantsWithNaNs / toInstants (sts_instants.hip)
 hipError_t launch_series_stats(const double* in, double* out, int64_t S, int64_t T, int64_t ld, hipStream_t st);

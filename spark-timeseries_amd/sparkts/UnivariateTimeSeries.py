@@ -2,7 +2,7 @@
 
 Same function names, argument meaning and exceptions as the Scala object; every
 function accepts one series (T,) or a whole panel (S, T) and dispatches ONE batched
-C-ABI call (include/sts.h, include/sts_transforms.h) -- torch GPU tensors take the device path on torch's
+C-ABI call (include/sts.h, include/sts_transforms.h, include/sts_roll.h) -- torch GPU tensors take the device path on torch's
 current stream, numpy arrays take the host-staging (`_host`) path.  Results are
 always fresh arrays, as in the reference.
 """
@@ -17,7 +17,8 @@ from .errors import UnsupportedOperationException
 __all__ = ["fillts", "fillLinear", "fillNearest", "fillNext", "fillPrevious", "fillSpline", "autocorr", "lag",
            "differencesAtLag", "ar", "fill_method_code", "quotients", "price2ret", "fillWithDefault", "downsample",
            "upsample", "firstNotNaN", "lastNotNaN", "trimLeading", "trimTrailing", "inverseDifferencesAtLag",
-           "differencesOfOrderD", "inverseDifferencesOfOrderD"]
+           "differencesOfOrderD", "inverseDifferencesOfOrderD", "rollSum", "rollMean", "rollVar", "rollStd", "rollMin",
+           "rollMax", "rollZScore"]
 
 
 def fill_method_code(method: str) -> int:
@@ -281,3 +282,46 @@ def differencesOfOrderD(ts, d: int):
 def inverseDifferencesOfOrderD(diffedTs, d: int):
     """S/UnivariateTimeSeries.scala:459-465: the sweeps i = d..1 of inverseDifferencesAtLag(_, _, 1, i)."""
     return _same_shape("inverseDifferencesOfOrderD", "sts_inverse_diff_order_d", diffedTs, d)
+
+
+# ---- rolling-window statistics (include/sts_roll.h; later releases of the reference grew rollSum /
+# rollMean).  out[t] belongs to the trailing window of n steps ending at t; fewer than minPeriods
+# (default n) non-NaN steps in it give NaN.  The result has ts's shape. ----
+
+def _roll(op, ts, n, minPeriods):
+    from .rolling import roll
+    return roll(ts, op, n, minPeriods)
+
+
+def rollSum(ts, n: int, minPeriods=None):
+    """The sum of the window's non-NaN values, in ascending order."""
+    return _roll("sum", ts, n, minPeriods)
+
+
+def rollMean(ts, n: int, minPeriods=None):
+    """rollSum over the count of non-NaN values."""
+    return _roll("mean", ts, n, minPeriods)
+
+
+def rollVar(ts, n: int, minPeriods=None):
+    """The sample variance (divisor count - 1) in the corrected two-pass form; exactly +0.0 on a
+    bit-constant window."""
+    return _roll("var", ts, n, minPeriods)
+
+
+def rollStd(ts, n: int, minPeriods=None):
+    """sqrt(rollVar): rolling volatility."""
+    return _roll("std", ts, n, minPeriods)
+
+
+def rollMin(ts, n: int, minPeriods=None):
+    return _roll("min", ts, n, minPeriods)
+
+
+def rollMax(ts, n: int, minPeriods=None):
+    return _roll("max", ts, n, minPeriods)
+
+
+def rollZScore(ts, n: int, minPeriods=None):
+    """(ts[t] - rollMean) / rollStd; NaN where ts[t] is NaN and on a constant window."""
+    return _roll("zscore", ts, n, minPeriods)

@@ -1,5 +1,5 @@
 """Loader and ctypes bindings for libsts_hip.so (the C ABI in include/sts.h, include/sts_transforms.h,
-include/sts_sample.h, include/sts_index.h, include/sts_regress.h and include/sts_cross.h).
+include/sts_sample.h, include/sts_index.h, include/sts_regress.h, include/sts_cross.h and include/sts_roll.h).
 
 This is the Python analogue of the JNI shim: plain pointers and
 sizes cross the boundary, no torch types.  There is deliberately NO fallback:
@@ -199,10 +199,26 @@ CROSS_SIGNATURES = {
 }
 CROSS_COV, CROSS_CORR = 0, 1
 
+# Rolling-window statistics, include/sts_roll.h, the seventh sibling header
+# (tests/test_roll_cpu.py holds this table to it).
+_ROLL_TAIL = [_c_int, _c_int, _c_int]            # window, min_periods, op
+_ROLL_Y = [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp]  # x, y, Sy, ld_y, out
+ROLL_SIGNATURES = {
+    "sts_roll_op_from_name": (_c_int, [ctypes.c_char_p]),
+    "sts_roll_pair_op_from_name": (_c_int, [ctypes.c_char_p]),
+    "sts_roll_stat": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64] + _ROLL_TAIL + [_c_vp]),
+    "sts_roll_pair": (_c_int, _ROLL_Y + [_c_i64, _c_i64, _c_i64, _c_i64] + _ROLL_TAIL + [_c_vp]),
+    "sts_roll_stat_host": (_c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i64] + _ROLL_TAIL),
+    "sts_roll_pair_host": (_c_int, _ROLL_Y + [_c_i64, _c_i64, _c_i64] + _ROLL_TAIL),
+}
+ROLL_OPS = ("sum", "mean", "var", "std", "min", "max", "zscore")
+ROLL_PAIR_OPS = ("cov", "corr", "beta")
+ROLL_MAX_WINDOW = 1024
+
 
 def _bind(handle):
     for table in (SIGNATURES, TRANSFORM_SIGNATURES, SAMPLE_SIGNATURES, INDEX_SIGNATURES, REGRESS_SIGNATURES,
-                  CROSS_SIGNATURES):
+                  CROSS_SIGNATURES, ROLL_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(handle, name)
             fn.restype = res

@@ -276,6 +276,63 @@ class TimeSeriesRDD:
         from .stats import cross
         return cross.corr(self.data, self._cross_other(other, "correlation"))
 
+    # --- rolling-window statistics (include/sts_roll.h): the same index and keys ---
+    def _roll(self, op, n, minPeriods=None, other=None):
+        from .rolling import roll
+        return self._derive(roll(self.data, op, n, minPeriods, other))
+
+    def rollSum(self, n: int, minPeriods=None) -> "TimeSeriesRDD":
+        """mapSeries(UnivariateTimeSeries.rollSum(_, n)): out[t] over the n steps ending at t."""
+        return self._roll("sum", n, minPeriods)
+
+    def rollMean(self, n: int, minPeriods=None) -> "TimeSeriesRDD":
+        return self._roll("mean", n, minPeriods)
+
+    def rollVar(self, n: int, minPeriods=None) -> "TimeSeriesRDD":
+        return self._roll("var", n, minPeriods)
+
+    def rollStd(self, n: int, minPeriods=None) -> "TimeSeriesRDD":
+        return self._roll("std", n, minPeriods)
+
+    def rollMin(self, n: int, minPeriods=None) -> "TimeSeriesRDD":
+        return self._roll("min", n, minPeriods)
+
+    def rollMax(self, n: int, minPeriods=None) -> "TimeSeriesRDD":
+        return self._roll("max", n, minPeriods)
+
+    def rollZScore(self, n: int, minPeriods=None) -> "TimeSeriesRDD":
+        return self._roll("zscore", n, minPeriods)
+
+    def _roll_other(self, other, name):
+        """`other` of rollCov / rollCorr / rollBeta: another TimeSeriesRDD with this one's index and
+        count, or one (T,) factor that every series shares."""
+        from .errors import IllegalArgumentException
+        T = int(self.data.shape[-1])
+        if isinstance(other, TimeSeriesRDD):
+            if tuple(int(v) for v in other.data.shape) != tuple(int(v) for v in self.data.shape):
+                raise IllegalArgumentException("%s: the other RDD is %s, this one %s"
+                                               % (name, tuple(other.data.shape), tuple(self.data.shape)))
+            if _is_datetime_index(self.index) and _is_datetime_index(other.index) and self.index != other.index:
+                raise IllegalArgumentException("%s: the two RDDs have different date-time indices" % name)
+            return other.data
+        shape = tuple(int(v) for v in getattr(other, "shape", ()))
+        if shape != (T,):
+            raise IllegalArgumentException("%s: other must be a TimeSeriesRDD or a (T,) factor with T=%d, got shape %s"
+                                           % (name, T, shape))
+        return other
+
+    def rollCov(self, other, n: int, minPeriods=None) -> "TimeSeriesRDD":
+        """The rolling sample covariance of every series with the same series of `other`, or with
+        the one factor `other`."""
+        return self._roll("cov", n, minPeriods, self._roll_other(other, "rollCov"))
+
+    def rollCorr(self, other, n: int, minPeriods=None) -> "TimeSeriesRDD":
+        return self._roll("corr", n, minPeriods, self._roll_other(other, "rollCorr"))
+
+    def rollBeta(self, other, n: int, minPeriods=None) -> "TimeSeriesRDD":
+        """The rolling slope of every series on `other`: beta against a market factor."""
+        return self._roll("beta", n, minPeriods, self._roll_other(other, "rollBeta"))
+
     def fillAndAutocorr(self, method: str, numLags: int):
         """fill(method) followed by autocorr of every filled series, fused into one pass
         over HBM.  Returns (filled TimeSeriesRDD, acf (S, K))."""
