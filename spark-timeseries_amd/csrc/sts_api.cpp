@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "sts_internal.hpp"
+#include "sts_factor_basis.hpp"
 #include "sts_index.hpp"
 
 namespace {
@@ -223,6 +224,43 @@ hipError_t timed(hipStream_t st, F&& launch) {
     const hipError_t e = launch();
     prof_mark(st);
     return e;
+}
+
+// bgtest / bptest / factor_ols: the factors' orthonormal bases (f.k x f.n doubles and aux_doubles more
+// each, and a status) go to a stream-ordered scratch, then run(s0, ns) takes the series that read
+// them.  One basis for shared factors; per-series factors in chunks of series whose bases fit
+// kBasisChunkBytes, so the scratch stays bounded and warm in the caches; none where the kernels
+// build each series' basis in LDS (own: one chunk, then).
+constexpr size_t kBasisChunkBytes = (size_t)256 << 20;
+
+template <class Run>
+int over_factor_bases(sts::FactorBasisArgs& f, int64_t S, bool own, int aux_doubles, hipStream_t st,
+                      const char* name, Run run) {
+    const size_t nq = (size_t)f.k * (size_t)f.n;
+    const size_t per_basis = (nq + (size_t)aux_doubles) * sizeof(double);
+    int64_t chunk = 1;
+    if (own) chunk = S;
+    else if (f.fs != 0) chunk = std::max<int64_t>(1, std::min<int64_t>(S, (int64_t)(kBasisChunkBytes / per_basis)));
+    const size_t nbasis = own ? 0 : (size_t)chunk;
+    Scratch sc(st);
+    HIP_TRY(sc.alloc((per_basis + sizeof(int32_t)) * nbasis), "hipMallocAsync(factor basis)");
+    f.basis = static_cast<double*>(sc.p);
+    double* end = f.basis + nq * nbasis;
+    if (aux_doubles) f.aux = end;
+    f.info = reinterpret_cast<int32_t*>(end + (size_t)aux_doubles * nbasis);
+    if (f.fs != 0) {
+        f.basis_stride = (int64_t)nq;
+        f.aux_stride = aux_doubles;
+        f.info_stride = 1;
+    } else {
+        chunk = S;   // the one basis serves every series
+    }
+    for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+        const int64_t ns = std::min<int64_t>(chunk, S - s0);
+        if (!own) HIP_TRY(sts::launch_factor_basis(f, s0, f.fs != 0 ? ns : 1, st), name);
+        HIP_TRY(timed(st, [&] { return run(s0, ns); }), name);
+    }
+    return STS_OK;
 }
 
 // fillts "spline" (sts_spline.hip): its own kernel, not a tile-kernel method.  err (device,
@@ -1682,26 +1720,27 @@ int sts_lb_test(const double* in, int64_t S, int64_t T, int64_t ld, int max_lag,
     return STS_OK;
 }
 
-// bgtest / bptest: the factors' orthonormal basis goes to a stream-ordered scratch (one for shared
-// factors; per-series factors in chunks of series whose bases fit kBasisChunkBytes, so the scratch
-// stays bounded and warm in the caches), then one workgroup per series
-constexpr size_t kBasisChunkBytes = (size_t)256 << 20;
-
-static int bgbp_test(bool bp, const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k,
-                     int64_t ld_f, int64_t fs, int max_lag, double* stat, double* pvalue, int32_t* err_per_series,
-                     void* stream) {
-    const char* name = bp ? "bptest" : "bgtest";
-    int r;
+// the factor panel of bgtest / bptest and of t5 / t6: k, ld_f, fs and the pointer
+static int factor_panel(const double* factors, int64_t S, int64_t T, int k, int64_t ld_f, int64_t fs, const char* name) {
     if (k < 1 || k > sts::kMaxFactors)
         return fail(STS_ERR_BAD_ARG, "%s: %d factors outside [1, %d]", name, k, sts::kMaxFactors);
-    if (!bp && (max_lag < 1 || max_lag > 31)) return fail(STS_ERR_BAD_ARG, "bgtest: maxLag %d outside [1, 31]", max_lag);
-    if ((r = stat_panel(resid, S, T, ld, stat, name))) return r;
     if (ld_f < T)
         return fail(STS_ERR_BAD_ARG, "%s: factor leading dimension %lld < T=%lld", name, (long long)ld_f, (long long)T);
     if (fs != 0 && fs < (int64_t)(k - 1) * ld_f + T)
         return fail(STS_ERR_BAD_ARG, "%s: factor series stride %lld overlaps (needs 0 or >= %lld)", name, (long long)fs,
                     (long long)((int64_t)(k - 1) * ld_f + T));
     if (S * T > 0 && !factors) return fail(STS_ERR_BAD_ARG, "%s: null factor pointer", name);
+    return STS_OK;
+}
+
+static int bgbp_test(bool bp, const double* resid, int64_t S, int64_t T, int64_t ld, const double* factors, int k,
+                     int64_t ld_f, int64_t fs, int max_lag, double* stat, double* pvalue, int32_t* err_per_series,
+                     void* stream) {
+    const char* name = bp ? "bptest" : "bgtest";
+    int r;
+    if ((r = factor_panel(factors, S, T, k, ld_f, fs, name))) return r;
+    if (!bp && (max_lag < 1 || max_lag > 31)) return fail(STS_ERR_BAD_ARG, "bgtest: maxLag %d outside [1, 31]", max_lag);
+    if ((r = stat_panel(resid, S, T, ld, stat, name))) return r;
     const int L = bp ? 0 : max_lag;
     const int64_t n_obs = T - L, cols = 1 + (int64_t)k + L;
     if (n_obs <= cols)
@@ -1713,32 +1752,11 @@ static int bgbp_test(bool bp, const double* resid, int64_t S, int64_t T, int64_t
     ErrSink es(err_per_series, S, st);
     if ((r = es.prepare())) return r;
     sts::BgBpArgs a{};
-    a.in = resid; a.S = S; a.T = T; a.ld = ld; a.factors = factors; a.ld_f = ld_f; a.fs = fs; a.k = k; a.L = L;
-    a.squares = bp; a.lo = L; a.n = n_obs; a.stat = stat; a.err = es.dev;
-    // scratch bases: one for shared factors, a chunk's worth for per-series factors -- none where the
-    // kernels build each series' basis in LDS (one chunk, then)
-    const bool own = sts::own_basis(a);
-    const size_t per_basis = (size_t)k * (size_t)n_obs * sizeof(double);
-    int64_t chunk = 1;
-    if (own) chunk = S;
-    else if (fs != 0) chunk = std::max<int64_t>(1, std::min<int64_t>(S, (int64_t)(kBasisChunkBytes / per_basis)));
-    Scratch sc(st);
-    const size_t nbasis = own ? 0 : (size_t)chunk;
-    HIP_TRY(sc.alloc(per_basis * nbasis + nbasis * sizeof(int32_t)), "hipMallocAsync(factor basis)");
-    a.basis = static_cast<double*>(sc.p);
-    a.info = reinterpret_cast<int32_t*>(a.basis + (size_t)k * (size_t)n_obs * nbasis);
-    if (fs == 0) {
-        HIP_TRY(sts::launch_factor_basis(a, 0, 1, st), name);
-        HIP_TRY(timed(st, [&] { return sts::launch_bgbp(a, 0, S, st); }), name);
-    } else {
-        a.basis_stride = (int64_t)k * n_obs;
-        a.info_stride = 1;
-        for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-            const int64_t ns = std::min<int64_t>(chunk, S - s0);
-            HIP_TRY(sts::launch_factor_basis(a, s0, ns, st), name);
-            HIP_TRY(timed(st, [&] { return sts::launch_bgbp(a, s0, ns, st); }), name);
-        }
-    }
+    a.in = resid; a.S = S; a.T = T; a.ld = ld; a.L = L; a.squares = bp; a.stat = stat; a.err = es.dev;
+    a.f.factors = factors; a.f.ld_f = ld_f; a.f.fs = fs; a.f.k = k; a.f.lo = L; a.f.n = n_obs;
+    if ((r = over_factor_bases(a.f, S, sts::own_basis(a), 0, st, name,
+                               [&](int64_t s0, int64_t ns) { return sts::launch_bgbp(a, s0, ns, st); })))
+        return r;
     if (pvalue) HIP_TRY(sts::launch_chi2_pvalue(stat, pvalue, S, bp ? k : L, st), name);
     return es.finish(name);
 }
@@ -1755,21 +1773,7 @@ int sts_bg_test(const double* resid, int64_t S, int64_t T, int64_t ld, const dou
 
 // ---- include/sts_regress.h ----
 
-// the factor panel of t5 / t6: k, ld_f, fs and the pointer
-static int factor_panel(const double* factors, int64_t S, int64_t T, int k, int64_t ld_f, int64_t fs, const char* name) {
-    if (k < 1 || k > sts::kMaxFactors)
-        return fail(STS_ERR_BAD_ARG, "%s: %d factors outside [1, %d]", name, k, sts::kMaxFactors);
-    if (ld_f < T)
-        return fail(STS_ERR_BAD_ARG, "%s: factor leading dimension %lld < T=%lld", name, (long long)ld_f, (long long)T);
-    if (fs != 0 && fs < (int64_t)(k - 1) * ld_f + T)
-        return fail(STS_ERR_BAD_ARG, "%s: factor series stride %lld overlaps (needs 0 or >= %lld)", name, (long long)fs,
-                    (long long)((int64_t)(k - 1) * ld_f + T));
-    if (S * T > 0 && !factors) return fail(STS_ERR_BAD_ARG, "%s: null factor pointer", name);
-    return STS_OK;
-}
-
-// g1.  Scratch as bgtest / bptest: one basis for shared factors, per-series factors in chunks of
-// series whose bases fit kBasisChunkBytes, none where the kernel builds each basis in LDS.
+// g1
 int sts_factor_ols(const double* y, int64_t S, int64_t T, int64_t ld, const double* factors, int k, int64_t ld_f,
                    int64_t fs, double* beta, int64_t ld_b, double* stderr_out, double* stats, double* resid, int64_t ld_r,
                    int32_t* err_per_series, void* stream) {
@@ -1791,30 +1795,12 @@ int sts_factor_ols(const double* y, int64_t S, int64_t T, int64_t ld, const doub
     ErrSink es(err_per_series, S, st);
     if ((r = es.prepare())) return r;
     sts::OlsArgs a{};
-    a.y = y; a.S = S; a.T = T; a.ld = ld; a.factors = factors; a.ld_f = ld_f; a.fs = fs; a.k = k;
+    a.y = y; a.S = S; a.T = T; a.ld = ld;
+    a.f.factors = factors; a.f.ld_f = ld_f; a.f.fs = fs; a.f.k = k; a.f.n = T;
     a.beta = beta; a.se = stderr_out; a.ld_b = ld_b; a.stats = stats; a.resid = resid; a.ld_r = ld_r; a.err = es.dev;
-    const bool own = sts::ols_regime(T, k, fs) == 2;
-    const size_t per_basis = ((size_t)k * (size_t)T + sts::kOlsAux) * sizeof(double);
-    int64_t chunk = 1;
-    if (own) chunk = S;
-    else if (fs != 0) chunk = std::max<int64_t>(1, std::min<int64_t>(S, (int64_t)(kBasisChunkBytes / per_basis)));
-    const size_t nbasis = own ? 0 : (size_t)chunk;
-    Scratch sc(st);
-    HIP_TRY(sc.alloc(per_basis * nbasis), "hipMallocAsync(factor basis)");
-    a.basis = static_cast<double*>(sc.p);
-    a.aux = a.basis + (size_t)k * (size_t)T * nbasis;
-    if (fs == 0) {
-        HIP_TRY(sts::launch_ols_basis(a, 0, 1, st), name);
-        HIP_TRY(timed(st, [&] { return sts::launch_ols(a, 0, S, st); }), name);
-    } else {
-        a.basis_stride = (int64_t)k * T;
-        a.aux_stride = sts::kOlsAux;
-        for (int64_t s0 = 0; s0 < S; s0 += chunk) {
-            const int64_t ns = std::min<int64_t>(chunk, S - s0);
-            HIP_TRY(sts::launch_ols_basis(a, s0, ns, st), name);
-            HIP_TRY(timed(st, [&] { return sts::launch_ols(a, s0, ns, st); }), name);
-        }
-    }
+    if ((r = over_factor_bases(a.f, S, sts::ols_regime(T, k, fs) == 2, sts::kOlsAux, st, name,
+                               [&](int64_t s0, int64_t ns) { return sts::launch_ols(a, s0, ns, st); })))
+        return r;
     return es.finish(name);
 }
 

@@ -307,8 +307,9 @@ struct ArimaHrArgs {
 hipError_t launch_arima_hr(const ArimaHrArgs& a, hipStream_t st);
 
 // statistical tests (sts_stattests.hip): one workgroup per series; series of up to kStatOneWave
-// steps live in one wave's LDS block, longer ones are swept from global memory
+// steps live in one wave's LDS block, longer ones are swept from global memory by kLongThreads
 constexpr int64_t kStatOneWave = 2560;
+constexpr int kLongThreads = 256;
 struct StatArgs {
     const double* in;
     int64_t S, T, ld;
@@ -327,46 +328,51 @@ hipError_t launch_lb(const double* acf, int64_t S, int64_t T, int K, double* sta
 // Breusch-Godfrey / Breusch-Pagan.  kMaxFactors bounds k: the kernels keep one accumulator and one
 // basis value per factor in registers (unrolled to this bound) and an LDS row of it per lag window.
 constexpr int kMaxFactors = STS_MAX_FACTORS;
-struct BgBpArgs {
-    const double* in;        // residual panel
-    int64_t S, T, ld;
+// A factor panel and the scratch its orthonormal bases go to (sts_factor_basis.hpp): what the tests
+// and the factor OLS share.  One basis for shared factors (fs == 0, every stride 0), else one per
+// series of a chunk, indexed from the chunk's first series.
+struct FactorBasisArgs {
     const double* factors;   // factor j of series s at factors[s * fs + j * ld_f + t]; fs == 0: shared
     int64_t ld_f, fs;
     int k;                   // factors, 1..kMaxFactors
+    int64_t lo, n;           // rows lo .. lo + n of the factors are used
+    double* basis;           // k x n per basis, basis b at basis + b * basis_stride
+    int64_t basis_stride;
+    int32_t* info;           // per basis 0 or STS_ERR_SINGULAR (rank deficient), b * info_stride
+    int64_t info_stride;
+    double* aux;             // null, or kOlsAux doubles per basis (R^-1, factor means, ...), b * aux_stride
+    int64_t aux_stride;
+};
+// per-series factors of a one-wave series whose basis fits the LDS budget behind the series: the
+// series' kernel builds it there (the OLS aux block rides on top), and no scratch basis is needed
+constexpr size_t kOwnBasisLds = 48 << 10;
+inline bool own_basis_fits(int64_t T, int k, int64_t n, int64_t fs) {
+    return fs != 0 && T <= kStatOneWave && (size_t)(T + k * n) * sizeof(double) <= kOwnBasisLds;
+}
+// bases of series s0 .. s0 + nb (nb = 1 and s0 = 0 for shared factors) into f.basis / f.info, and
+// into f.aux where it is not null
+hipError_t launch_factor_basis(const FactorBasisArgs& f, int64_t s0, int64_t nb, hipStream_t st);
+
+struct BgBpArgs {
+    const double* in;        // residual panel
+    int64_t S, T, ld;
+    FactorBasisArgs f;       // lo = L, n = T - L; no aux
     int L;                   // BG: maxLag; BP: 0
     bool squares;            // BP: the response is e^2
-    int64_t lo, n;           // rows lo .. lo + n of the factors are used (lo = L, n = T - L)
-    double* basis;           // scratch: k x n per basis, basis b at basis + b * basis_stride
-    int64_t basis_stride;    // 0: one basis for every series
-    int32_t* info;           // scratch: per basis 0 or STS_ERR_SINGULAR
-    int64_t info_stride;     // 0 or 1
     double* stat;            // S
     int32_t* err;            // per-series status, zeroed by the caller
 };
-// true when launch_bgbp's kernels build each series' basis in LDS themselves (per-series factors of
-// short series): launch_factor_basis is then a no-op and basis / info are not used
-bool own_basis(const BgBpArgs& a);
-// bases of series s0 .. s0 + nb (nb = 1 and s0 = 0 for shared factors) into a.basis / a.info
-hipError_t launch_factor_basis(const BgBpArgs& a, int64_t s0, int64_t nb, hipStream_t st);
-// statistics of series s0 .. s0 + ns; basis / info are indexed from the chunk's first series
+// true when launch_bgbp's kernels build each series' basis in LDS themselves: the scratch is not used
+inline bool own_basis(const BgBpArgs& a) { return own_basis_fits(a.T, a.f.k, a.f.n, a.f.fs); }
+// statistics of series s0 .. s0 + ns
 hipError_t launch_bgbp(const BgBpArgs& a, int64_t s0, int64_t ns, hipStream_t st);
 hipError_t launch_chi2_pvalue(const double* stat, double* pv, int64_t S, int dof, hipStream_t st);
-// A remainder of at most this share of the centred column counts as none: twice-applied
-// Gram-Schmidt leaves rounding noise of a few ulps of the column where exact arithmetic leaves 0
-// (a duplicated factor), and a factor collinear to 1e-6 leaves a million times the bound.
-constexpr double kBasisTol2 = 0x1p-80;   // (2^-40)^2, on squared norms
 
 // OLS of a panel on factors and the effects pair (sts_regress.hip, include/sts_regress.h)
 struct OlsArgs {
     const double* y;
     int64_t S, T, ld;
-    const double* factors;   // as BgBpArgs
-    int64_t ld_f, fs;
-    int k;
-    double* basis;           // scratch: k x T per basis, basis b at basis + b * basis_stride
-    int64_t basis_stride;    // 0: one basis for every series
-    double* aux;             // scratch: kOlsAux doubles per basis (R^-1, factor means, ...), b * aux_stride
-    int64_t aux_stride;      // 0 or kOlsAux
+    FactorBasisArgs f;       // lo = 0, n = T; with aux
     double* beta;            // S x (k + 1) at ld_b
     double* se;              // optional, as beta
     int64_t ld_b;
@@ -375,15 +381,12 @@ struct OlsArgs {
     int64_t ld_r;
     int32_t* err;            // per-series status, zeroed by the caller
 };
-constexpr int kOlsAux = 152;
 // which of launch_ols's kernels a call takes (tests name the seams): 0 = shared factors, several
 // waves per workgroup with the basis staged in LDS; 1 = one wave per series, basis in the scratch;
 // 2 = one wave per series that builds its own factors' basis in LDS (no scratch); 3 = 256-thread
 // sweeps over global memory
 int ols_regime(int64_t T, int k, int64_t fs);
-// bases (with R^-1 and the means) of series s0 .. s0 + nb into a.basis / a.aux; a no-op in regime 2
-hipError_t launch_ols_basis(const OlsArgs& a, int64_t s0, int64_t nb, hipStream_t st);
-// fits of series s0 .. s0 + ns; basis / aux are indexed from the chunk's first series
+// fits of series s0 .. s0 + ns
 hipError_t launch_ols(const OlsArgs& a, int64_t s0, int64_t ns, hipStream_t st);
 hipError_t launch_factor_effects(bool add, const double* in, double* out, int64_t S, int64_t T, int64_t ld_in,
                                  int64_t ld_out, const double* factors, int k, int64_t ld_f, int64_t fs,

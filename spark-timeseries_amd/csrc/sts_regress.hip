@@ -2,16 +2,15 @@
 // the effects pair that applies fitted coefficients (g2).  What the results are held to is
 // commons-math3 3.4.1 OLSMultipleLinearRegression with intercept.
 //
-// Numerical form.  The factors' centred columns get an orthonormal basis Q by
-// the Gram-Schmidt of sts_stattests.hip's build_basis, operation for operation, and here the
-// triangular factor is kept: F_c = Q R, R[c][j] the sum of the two coefficients of column j on q_c,
-// R[j][j] the remaining norm.  With y_c the series centred on y - y[0] (and the rounding-level rest of its mean
-// taken out of the intercept and the residuals):
+// Numerical form.  The factors' centred columns get the orthonormal basis Q
+// of sts_factor_basis.hpp, the one bgtest / bptest use, with the triangular factor kept: F_c = Q R.
+// With y_c the series centred on y - y[0] (and the rounding-level rest of its mean taken out of the
+// intercept and the residuals):
 //   c = Q'y_c,  beta_F = R^-1 c,  b0 = ybar - beta_F . fbar,  resid = y_c - sum_j c_j q_j (explicit),
 //   rss = sum resid^2 (never tss - ess),  r2 = ess / tss with ess = sum c_j^2,
 //   se_F[j]^2 = sigma2 |row j of R^-1|^2,  se_0^2 = sigma2 (1 / T + |R^-T fbar|^2).
 // Everything that depends on the factors alone (Q, R^-1, fbar, the row norms, 1/T + |R^-T fbar|^2)
-// is built once per factor matrix (OlsArgs::aux).
+// is built once per factor matrix (FactorBasisArgs::aux).
 //
 // One kernel body, four regimes (ols_regime):
 //   0  shared factors whose basis fits LDS next to kHotWaves series: the hot path.  A workgroup of
@@ -29,6 +28,7 @@
 #include <cstdint>
 
 #include "sts_elementwise.hpp"
+#include "sts_factor_basis.hpp"
 #include "sts_internal.hpp"
 #include "sts_wgsum.hpp"
 
@@ -44,106 +44,9 @@
 namespace sts {
 namespace {
 
-constexpr int kLongThreads = 256;
 constexpr int kHotWaves = STS_OLS_WAVES > 0 ? STS_OLS_WAVES : 1;
 constexpr int kHotSeriesPerWave = STS_OLS_SPW;
 constexpr size_t kStageLds = 60 << 10;      // regime 0: basis + kHotWaves series
-constexpr size_t kOwnBasisLds = 48 << 10;   // regime 2: series + basis (the aux block rides on top)
-
-// OlsArgs::aux, per basis; rows of the k x k blocks are kMaxFactors apart
-constexpr int kAuxRinv = 0;     // R^-1, upper triangle
-constexpr int kAuxMean = 64;    // fbar
-constexpr int kAuxRow2 = 72;    // |row i of R^-1|^2
-constexpr int kAuxH = 80;       // 1 / n + |R^-T fbar|^2
-constexpr int kAuxFlag = 81;    // nonzero: rank deficient
-constexpr int kAuxR = 88;       // R itself (working storage of the builder)
-static_assert(kAuxR + kMaxFactors * kMaxFactors == kOlsAux && kMaxFactors == 8, "aux layout");
-
-// build_basis of sts_stattests.hip with the triangular factor, the means and what the fit derives
-// from them kept in aux (global scratch or LDS); true when the factors are rank deficient.  Thread 0
-// alone writes and re-reads aux; callers order it against the other threads' reads.
-template <int NT>
-__device__ __forceinline__ bool build_basis_r(const double* __restrict__ F, int64_t ld_f, int k, int64_t n, double* Q,
-                                              double* aux, double* red) {
-    const int tid = threadIdx.x;
-    const double dn = (double)n;
-    bool singular = false;
-    for (int j = 0; j < k && !singular; j++) {
-        const double* __restrict__ f = F + (int64_t)j * ld_f;
-        double* q = Q + (int64_t)j * n;
-        const double f0 = f[0];
-        double acc = 0.0;
-        for (int64_t i = tid; i < n; i += NT) acc += f[i] - f0;
-        const double mu = bsum<NT>(acc, red) / dn;
-        acc = 0.0;
-        for (int64_t i = tid; i < n; i += NT) {
-            const double v = (f[i] - f0) - mu;
-            q[i] = v;
-            acc += v;
-        }
-        const double mu2 = bsum<NT>(acc, red) / dn;
-        acc = 0.0;
-        for (int64_t i = tid; i < n; i += NT) {
-            const double v = q[i] - mu2;
-            q[i] = v;
-            acc += v * v;
-        }
-        const double c2 = bsum<NT>(acc, red);
-        if (tid == 0) aux[kAuxMean + j] = f0 + (mu + mu2);
-        for (int pass = 0; pass < 2; pass++)
-            for (int c = 0; c < j; c++) {
-                const double* qc = Q + (int64_t)c * n;
-                acc = 0.0;
-                for (int64_t i = tid; i < n; i += NT) acc += qc[i] * q[i];
-                const double d = bsum<NT>(acc, red);
-                for (int64_t i = tid; i < n; i += NT) q[i] -= d * qc[i];
-                if (tid == 0) aux[kAuxR + c * kMaxFactors + j] = pass == 0 ? d : aux[kAuxR + c * kMaxFactors + j] + d;
-            }
-        acc = 0.0;
-        for (int64_t i = tid; i < n; i += NT) acc += q[i] * q[i];
-        const double w2 = bsum<NT>(acc, red);
-        if (w2 <= kBasisTol2 * c2) {   // uniform; NaN passes (NaN in, NaN out, status 0)
-            singular = true;
-            break;
-        }
-        const double w = sqrt(w2);
-        for (int64_t i = tid; i < n; i += NT) q[i] /= w;
-        if (tid == 0) aux[kAuxR + j * kMaxFactors + j] = w;
-    }
-    if (tid == 0) {
-        aux[kAuxFlag] = singular ? 1.0 : 0.0;
-        if (!singular) {
-            const double* R = aux + kAuxR;
-            double* inv = aux + kAuxRinv;
-            // back substitution per unit column
-            for (int c = 0; c < k; c++)
-                for (int r = c; r >= 0; r--) {
-                    double v = r == c ? 1.0 : 0.0;
-                    for (int j = r + 1; j <= c; j++) v -= R[r * kMaxFactors + j] * inv[j * kMaxFactors + c];
-                    inv[r * kMaxFactors + c] = v / R[r * kMaxFactors + r];
-                }
-            double h = 0.0;
-            for (int i = 0; i < k; i++) {
-                double r2 = 0.0, wi = 0.0;
-                for (int j = i; j < k; j++) r2 += inv[i * kMaxFactors + j] * inv[i * kMaxFactors + j];
-                for (int r = 0; r <= i; r++) wi += inv[r * kMaxFactors + i] * aux[kAuxMean + r];   // (R^-T fbar)[i]
-                aux[kAuxRow2 + i] = r2;
-                h += wi * wi;
-            }
-            aux[kAuxH] = 1.0 / dn + h;
-        }
-    }
-    return singular;
-}
-
-// One workgroup per factor matrix, into the scratch
-template <int NT>
-__global__ __launch_bounds__(NT) void ols_basis_kernel(OlsArgs a, int64_t s0) {
-    __shared__ double red[4];
-    const int64_t b = blockIdx.x;
-    (void)build_basis_r<NT>(a.factors + (s0 + b) * a.fs, a.ld_f, a.k, a.T, a.basis + b * a.basis_stride,
-                            a.aux + b * a.aux_stride, red);
-}
 
 // The fit of one series by NT threads (tid of them): g its T values, Q / aux its basis, ys its LDS
 // row when YLDS; k <= KB, the bound the per-factor registers are unrolled to.  Every reduced value is
@@ -152,7 +55,7 @@ template <int NT, bool YLDS, int KB>
 __device__ __forceinline__ void ols_fit(const OlsArgs& a, int64_t s, int tid, const double* __restrict__ g,
                                         const double* Q, const double* aux, bool singular, double* ys, double* red) {
     const int64_t T = a.T;
-    const int k = a.k;
+    const int k = a.f.k;
     double* beta = a.beta + s * a.ld_b;
     double* se = a.se ? a.se + s * a.ld_b : nullptr;
     double* stats = a.stats ? a.stats + s * 4 : nullptr;
@@ -251,11 +154,13 @@ __global__ __launch_bounds__(NT* NW) void ols_kernel(OlsArgs a, int64_t s0, int6
     const int tid = NW > 1 ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
     const int w = NW > 1 ? (int)(threadIdx.x >> 6) : 0;
     const int64_t T = a.T;
-    const int k = a.k;
+    const int k = a.f.k;
+    bool shared_singular = false;
     if constexpr (QMODE == 1) {
         const int64_t nq = (int64_t)k * T;
-        for (int64_t i = threadIdx.x; i < nq; i += NT * NW) dyn[i] = a.basis[i];
-        for (int i = threadIdx.x; i < kAuxR; i += NT * NW) dyn[nq + i] = a.aux[i];   // what the fits read of it
+        for (int64_t i = threadIdx.x; i < nq; i += NT * NW) dyn[i] = a.f.basis[i];
+        for (int i = threadIdx.x; i < kAuxR; i += NT * NW) dyn[nq + i] = a.f.aux[i];   // what the fits read of it
+        shared_singular = a.f.info[0] != 0;
         __syncthreads();
     }
     double* ys = QMODE == 1 ? dyn + (int64_t)k * T + kAuxR + (int64_t)w * T : dyn;
@@ -270,14 +175,14 @@ __global__ __launch_bounds__(NT* NW) void ols_kernel(OlsArgs a, int64_t s0, int6
         if constexpr (QMODE == 2) {
             double* q = dyn + T;
             double* ax = q + (int64_t)k * T;
-            singular = build_basis_r<NT>(a.factors + s * a.fs, a.ld_f, k, T, q, ax, red);
+            singular = build_basis<NT, true>(a.f.factors + s * a.f.fs, a.f.ld_f, k, T, q, ax, red);
             __syncthreads();   // thread 0's aux
             Q = q;
             aux = ax;
         } else {
-            aux = QMODE == 1 ? dyn + (int64_t)k * T : a.aux + b * a.aux_stride;
-            singular = aux[kAuxFlag] != 0.0;
-            Q = QMODE == 1 ? dyn : a.basis + b * a.basis_stride;
+            aux = QMODE == 1 ? dyn + (int64_t)k * T : a.f.aux + b * a.f.aux_stride;
+            singular = QMODE == 1 ? shared_singular : a.f.info[b * a.f.info_stride] != 0;
+            Q = QMODE == 1 ? dyn : a.f.basis + b * a.f.basis_stride;
         }
         ols_fit<NT, YLDS, KB>(a, s, tid, a.y + s * a.ld, Q, aux, singular, ys, red);
     }
@@ -306,19 +211,13 @@ __global__ __launch_bounds__(kThreads) void factor_effects_kernel(const double* 
 int ols_regime(int64_t T, int k, int64_t fs) {
     if (T > kStatOneWave) return 3;
     if (fs == 0) return STS_OLS_WAVES > 0 && (size_t)(kHotWaves + k) * (size_t)T * sizeof(double) <= kStageLds ? 0 : 1;
-    return (size_t)(T + (int64_t)k * T) * sizeof(double) <= kOwnBasisLds ? 2 : 1;
-}
-
-hipError_t launch_ols_basis(const OlsArgs& a, int64_t s0, int64_t nb, hipStream_t st) {
-    if (ols_regime(a.T, a.k, a.fs) == 2) return hipSuccess;
-    hipLaunchKernelGGL(ols_basis_kernel<kLongThreads>, dim3((unsigned)nb), dim3(kLongThreads), 0, st, a, s0);
-    return hipGetLastError();
+    return own_basis_fits(T, k, T, fs) ? 2 : 1;
 }
 
 // the kernel of a regime, its per-factor registers unrolled to 4 (k <= 4) or to kMaxFactors
 template <int NT, int NW, bool YLDS, int QMODE>
 static void launch_ols_kernel(const OlsArgs& a, int64_t s0, int64_t ns, int spw, int64_t blocks, size_t lds, hipStream_t st) {
-    if (a.k <= 4)
+    if (a.f.k <= 4)
         hipLaunchKernelGGL((ols_kernel<NT, NW, YLDS, QMODE, 4>), dim3((unsigned)blocks), dim3(NT * NW), lds, st, a, s0, ns, spw);
     else
         hipLaunchKernelGGL((ols_kernel<NT, NW, YLDS, QMODE, kMaxFactors>), dim3((unsigned)blocks), dim3(NT * NW), lds, st, a,
@@ -327,21 +226,21 @@ static void launch_ols_kernel(const OlsArgs& a, int64_t s0, int64_t ns, int spw,
 
 hipError_t launch_ols(const OlsArgs& a, int64_t s0, int64_t ns, hipStream_t st) {
     const size_t row = (size_t)a.T * sizeof(double);
-    switch (ols_regime(a.T, a.k, a.fs)) {
+    switch (ols_regime(a.T, a.f.k, a.f.fs)) {
     case 0: {
         // enough workgroups to fill the chip before a wave takes a second series
         const int64_t want = ns / ((int64_t)kHotWaves * 2048);
         const int spw = (int)(want < 1 ? 1 : want > kHotSeriesPerWave ? kHotSeriesPerWave : want);
         const int64_t per = (int64_t)kHotWaves * spw;
         launch_ols_kernel<64, kHotWaves, true, 1>(a, s0, ns, spw, (ns + per - 1) / per,
-                                                  (size_t)(kHotWaves + a.k) * row + kAuxR * sizeof(double), st);
+                                                  (size_t)(kHotWaves + a.f.k) * row + kAuxR * sizeof(double), st);
         break;
     }
     case 1:
         launch_ols_kernel<64, 1, true, 0>(a, s0, ns, 1, ns, row, st);
         break;
     case 2:
-        launch_ols_kernel<64, 1, true, 2>(a, s0, ns, 1, ns, (size_t)(1 + a.k) * row + kOlsAux * sizeof(double), st);
+        launch_ols_kernel<64, 1, true, 2>(a, s0, ns, 1, ns, (size_t)(1 + a.f.k) * row + kOlsAux * sizeof(double), st);
         break;
     default:
         launch_ols_kernel<kLongThreads, 1, false, 0>(a, s0, ns, 1, ns, 0, st);

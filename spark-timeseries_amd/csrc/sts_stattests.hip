@@ -21,13 +21,13 @@
 #include <cmath>
 #include <cstdint>
 
+#include "sts_factor_basis.hpp"
 #include "sts_internal.hpp"
 #include "sts_wgsum.hpp"
 
 namespace sts {
 namespace {
 
-constexpr int kLongThreads = 256;
 constexpr int kMaxCols = 33;   // ADF: 31 lags + level + response
 
 // ---- workgroup-wide inclusive scan (the sums: sts_wgsum.hpp) ----
@@ -182,6 +182,28 @@ __global__ __launch_bounds__(NT) void kpss_kernel(StatArgs a) {
     if (tid == 0) a.stat[s] = (s2 / lrv) / (n * n);
 }
 
+// Cholesky of the lag block G[0..nl)[0..nl) of a Gram matrix, one thread per row; rows nl..m, the
+// right-hand sides, become L^-1 X_lags' of them.  The diagonal goes to dg unless it is null.  True
+// (uniform) at an exactly zero or negative pivot, the reference's SingularMatrixException; NaN
+// pivots pass (NaN in, NaN out, status 0).
+__device__ __forceinline__ bool lag_cholesky(double (*G)[kMaxCols + 1], int nl, int m, double* dg) {
+    const int tid = threadIdx.x;
+    for (int j = 0; j < nl; j++) {
+        double d2 = G[j][j];
+        for (int c = 0; c < j; c++) d2 -= G[j][c] * G[j][c];
+        if (d2 <= 0.0) return true;
+        const double d = sqrt(d2);
+        if (tid > j && tid < m) {
+            double v = G[tid][j];
+            for (int c = 0; c < j; c++) v -= G[tid][c] * G[j][c];
+            G[tid][j] = v / d;
+        }
+        if (dg && tid == 0) dg[j] = d;
+        __syncthreads();
+    }
+    return false;
+}
+
 // ---- ADF (:204-232), Frisch-Waugh two-pass ----
 // Rows i = 0..n-1 (n = T - 1 - p), d[t] = y[t+1] - y[t]:
 //   level    y[p + i]            (the reference's column 0)
@@ -320,26 +342,8 @@ __global__ __launch_bounds__(NT) void adf_kernel(StatArgs a) {
         }
     }
     __syncthreads();
-    // Cholesky of the lag block, one thread per row; rows p and p + 1 become L^-1 X_lags' (level,
-    // response).  An exactly zero (or negative) pivot is the reference's SingularMatrixException;
-    // NaN pivots pass (NaN in, NaN out, status 0).
-    bool singular = false;
-    for (int j = 0; j < p; j++) {
-        double d2 = G[j][j];
-        for (int k = 0; k < j; k++) d2 -= G[j][k] * G[j][k];
-        if (d2 <= 0.0) {
-            singular = true;
-            break;
-        }
-        const double d = sqrt(d2);
-        if (tid > j && tid < m) {
-            double v = G[tid][j];
-            for (int k = 0; k < j; k++) v -= G[tid][k] * G[j][k];
-            G[tid][j] = v / d;
-        }
-        if (tid == 0) dg[j] = d;
-        __syncthreads();
-    }
+    // rows p and p + 1 become L^-1 X_lags' (level, response)
+    bool singular = lag_cholesky(G, p, m, dg);
     // back substitution: gam[w] = the lag coefficients of the level (w = 0) and the response (w = 1)
     if (!singular && tid < 2) {
         for (int c = p - 1; c >= 0; c--) {
@@ -477,66 +481,6 @@ __global__ void lb_kernel(const double* __restrict__ acf, int64_t S, int64_t T, 
 // adf_kernel).  No term is a difference of large numbers, so R^2 keeps its relative accuracy
 // where 1 - RSS / TSS and a pivot of the whole Gram matrix lose theirs.
 
-// The orthonormal basis of one factor matrix: Q (k x n, row c at Q + c * n; global scratch or LDS),
-// from rows 0..n of the k factor rows at F; true when the factors are rank deficient.  Each thread
-// owns its rows i = tid, tid + NT, .. of every column, so the in-place sweeps need no ordering
-// between threads; only the dot products cross lanes.
-template <int NT>
-__device__ __forceinline__ bool build_basis(const double* __restrict__ F, int64_t ld_f, int k, int64_t n, double* Q,
-                                            double* red) {
-    const int tid = threadIdx.x;
-    const double dn = (double)n;
-    for (int j = 0; j < k; j++) {
-        const double* __restrict__ f = F + (int64_t)j * ld_f;
-        double* q = Q + (int64_t)j * n;
-        // centred column: sums on f - f[0] so that the level does not eat the spread's digits
-        const double f0 = f[0];
-        double acc = 0.0;
-        for (int64_t i = tid; i < n; i += NT) acc += f[i] - f0;
-        const double mu = bsum<NT>(acc, red) / dn;
-        acc = 0.0;
-        for (int64_t i = tid; i < n; i += NT) {
-            const double v = (f[i] - f0) - mu;
-            q[i] = v;
-            acc += v;
-        }
-        const double mu2 = bsum<NT>(acc, red) / dn;
-        acc = 0.0;
-        for (int64_t i = tid; i < n; i += NT) {
-            const double v = q[i] - mu2;
-            q[i] = v;
-            acc += v * v;
-        }
-        const double c2 = bsum<NT>(acc, red);
-        // modified Gram-Schmidt against the earlier columns, twice
-        for (int pass = 0; pass < 2; pass++)
-            for (int c = 0; c < j; c++) {
-                const double* qc = Q + (int64_t)c * n;
-                acc = 0.0;
-                for (int64_t i = tid; i < n; i += NT) acc += qc[i] * q[i];
-                const double d = bsum<NT>(acc, red);
-                for (int64_t i = tid; i < n; i += NT) q[i] -= d * qc[i];
-            }
-        acc = 0.0;
-        for (int64_t i = tid; i < n; i += NT) acc += q[i] * q[i];
-        const double w2 = bsum<NT>(acc, red);
-        if (w2 <= kBasisTol2 * c2) return true;   // uniform; NaN passes (NaN in, NaN out, status 0)
-        const double w = sqrt(w2);
-        for (int64_t i = tid; i < n; i += NT) q[i] /= w;
-    }
-    return false;
-}
-
-// One workgroup per factor matrix, into the scratch: a.basis, a.info (0 or STS_ERR_SINGULAR)
-template <int NT>
-__global__ __launch_bounds__(NT) void factor_basis_kernel(BgBpArgs a, int64_t s0) {
-    __shared__ double red[4];
-    const int64_t b = blockIdx.x;
-    const bool singular = build_basis<NT>(a.factors + (s0 + b) * a.fs + a.lo, a.ld_f, a.k, a.n,
-                                          a.basis + b * a.basis_stride, red);
-    if (threadIdx.x == 0) a.info[b] = singular ? STS_ERR_SINGULAR : 0;
-}
-
 // The basis of a stat kernel's series: OWN builds it from the series' own factors into LDS behind
 // the series (per-series factors that fit, one-wave form); otherwise it is in the scratch.  False
 // when the factors are rank deficient (the statistic is then NaN, the status STS_ERR_SINGULAR).
@@ -545,11 +489,11 @@ __device__ __forceinline__ bool series_basis(const BgBpArgs& a, int64_t s, int64
                                              const double*& Q) {
     bool singular;
     if constexpr (OWN) {
-        singular = build_basis<NT>(a.factors + s * a.fs + a.lo, a.ld_f, a.k, a.n, lds, red);
+        singular = build_basis<NT, false>(a.f.factors + s * a.f.fs + a.f.lo, a.f.ld_f, a.f.k, a.f.n, lds, nullptr, red);
         Q = lds;
     } else {
-        singular = a.info[b * a.info_stride] != 0;
-        Q = a.basis + b * a.basis_stride;
+        singular = a.f.info[b * a.f.info_stride] != 0;
+        Q = a.f.basis + b * a.f.basis_stride;
     }
     if (singular && threadIdx.x == 0) {
         a.stat[s] = NAN;
@@ -569,8 +513,8 @@ __global__ __launch_bounds__(NT) void bg_kernel(BgBpArgs a, int64_t s0) {
     __shared__ double G[kMaxCols][kMaxCols + 1];
     const int64_t b = blockIdx.x, s = s0 + b;
     const double* __restrict__ g = a.in + s * a.ld;
-    const int64_t T = a.T, n = a.n;
-    const int tid = threadIdx.x, L = a.L, k = a.k;
+    const int64_t T = a.T, n = a.f.n;
+    const int tid = threadIdx.x, L = a.L, k = a.f.k;
     const double dn = (double)n;
     const double* Q;
     if (!series_basis<NT, OWN>(a, s, b, dyn + T, red, Q)) return;   // uniform
@@ -669,23 +613,7 @@ __global__ __launch_bounds__(NT) void bg_kernel(BgBpArgs a, int64_t s0) {
             }
         }
         __syncthreads();
-        // Cholesky of the lag block, one thread per row; row L becomes Lz^-1 Z'z_0.  A zero or
-        // negative pivot is the reference's SingularMatrixException; NaN pivots pass.
-        for (int j = 0; j < L; j++) {
-            double d2 = G[j][j];
-            for (int c = 0; c < j; c++) d2 -= G[j][c] * G[j][c];
-            if (d2 <= 0.0) {
-                singular = true;
-                break;
-            }
-            const double d = sqrt(d2);
-            if (tid > j && tid <= L) {
-                double v = G[tid][j];
-                for (int c = 0; c < j; c++) v -= G[tid][c] * G[j][c];
-                G[tid][j] = v / d;
-            }
-            __syncthreads();
-        }
+        singular = lag_cholesky(G, L, L + 1, nullptr);   // row L becomes Lz^-1 Z'z_0
         if (!singular)
             for (int j = 0; j < L; j++) ess += G[L][j] * G[L][j];
     }
@@ -709,7 +637,7 @@ __global__ __launch_bounds__(NT) void bp_kernel(BgBpArgs a, int64_t s0) {
     const int64_t b = blockIdx.x, s = s0 + b;
     const double* __restrict__ g = a.in + s * a.ld;
     const int64_t T = a.T;
-    const int tid = threadIdx.x, k = a.k;
+    const int tid = threadIdx.x, k = a.f.k;
     const double dn = (double)T;
     const double* Q;
     if (!series_basis<NT, OWN>(a, s, b, dyn + T, red, Q)) return;   // uniform
@@ -760,22 +688,16 @@ __global__ void chi2_pvalue_kernel(const double* __restrict__ stat, double* __re
 
 }  // namespace
 
-// per-series factors of a one-wave series whose basis fits the LDS budget next to the series: the
-// stat kernel builds it there, and no scratch basis is needed
-constexpr size_t kOwnBasisLds = 48 << 10;
-bool own_basis(const BgBpArgs& a) {
-    return a.fs != 0 && a.T <= kStatOneWave && (size_t)(a.T + a.k * a.n) * sizeof(double) <= kOwnBasisLds;
-}
-
-hipError_t launch_factor_basis(const BgBpArgs& a, int64_t s0, int64_t nb, hipStream_t st) {
-    if (own_basis(a)) return hipSuccess;
-    hipLaunchKernelGGL(factor_basis_kernel<kLongThreads>, dim3((unsigned)nb), dim3(kLongThreads), 0, st, a, s0);
+hipError_t launch_factor_basis(const FactorBasisArgs& f, int64_t s0, int64_t nb, hipStream_t st) {
+    const dim3 grid((unsigned)nb), block(kLongThreads);
+    if (f.aux) hipLaunchKernelGGL((factor_basis_kernel<kLongThreads, true>), grid, block, 0, st, f, s0);
+    else hipLaunchKernelGGL((factor_basis_kernel<kLongThreads, false>), grid, block, 0, st, f, s0);
     return hipGetLastError();
 }
 
 hipError_t launch_bgbp(const BgBpArgs& a, int64_t s0, int64_t ns, hipStream_t st) {
     const dim3 grid((unsigned)ns);
-    const size_t series = (size_t)a.T * sizeof(double), own = (size_t)(a.T + a.k * a.n) * sizeof(double);
+    const size_t series = (size_t)a.T * sizeof(double), own = (size_t)(a.T + a.f.k * a.f.n) * sizeof(double);
     if (a.squares) {
         if (own_basis(a)) hipLaunchKernelGGL((bp_kernel<64, true, true>), grid, dim3(64), own, st, a, s0);
         else if (a.T <= kStatOneWave) hipLaunchKernelGGL((bp_kernel<64, true, false>), grid, dim3(64), series, st, a, s0);

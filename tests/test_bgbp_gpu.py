@@ -255,6 +255,28 @@ def test_shared_and_replicated_factors_agree(torch, T, lag):
     assert_close(repl, want, 1e-10, "replicated")
 
 
+# ---- the scratch's chunk seam ----
+
+@pytest.mark.parametrize("lag", [None, 4])
+def test_basis_chunk_seam(torch, lag):
+    """Per-series factors one chunk of scratch bases and more: k = 8, T = 8192 is 524 288 bytes per basis
+    (BP; 524 032 at lag 4), 512 bases to the 256 MiB bound, so S = 600 takes two chunks (512 + 88).  The
+    series around the seam and at the ends against the restatement and, bit for bit, against a call of
+    their own (S = 1)."""
+    S, T, k = 600, 8192, 8
+    F = br.factors(99, T, k, S)
+    e = br.bp_resid(98, S, T, F) if lag is None else br.bg_resid(97, S, T)
+    err = torch.full((S,), -1, dtype=torch.int32, device="cuda:0")
+    st, stat, _ = call(torch, e, F, lag, want_p=False, err=err)
+    assert st == OK and not err.cpu().numpy().any()
+    assert np.isfinite(stat).all()
+    rows = [0, 511, 512, 513, 599]
+    assert_close(stat[rows], ref_stats(e[rows], F[rows], lag), 1e-10, "chunk seam, lag %s" % lag)
+    for s in rows:
+        st, one, _ = call(torch, e[s:s + 1], F[s:s + 1], lag, want_p=False)
+        assert st == OK and one.view(np.uint64)[0] == stat.view(np.uint64)[s], s
+
+
 # ---- per-series outcomes ----
 
 NB_T, NB_S, NB_K, NB_LAG = 129, 6, 3, 4

@@ -9,9 +9,9 @@ measured in the SAME process, alternating call by call with the case being measu
                              sts_factor_remove itself, and sts_fill (linear) on the NaN-free panel
   sts_factor_remove          sts_diff_at_lag (lag 1)
 
---other-lib PATH adds, for the shared-factor cases, the same call in ANOTHER build of the library
-(e.g. tools/variant.sh ... -DSTS_OLS_WAVES=0: one 64-thread workgroup per series) as the yardstick,
-alternating in this one process.
+--other-lib PATH adds the same call in ANOTHER build of the library as the yardstick, alternating in
+this one process (e.g. tools/variant.sh ... -DSTS_OLS_WAVES=0: one 64-thread workgroup per series,
+or the parent commit's build), for shared and per-series factors; --cases other runs only those.
 
 --parent-lib PATH adds the fit-only cases against sts_bp_test of THAT build (the parent commit's
 library: the yardstick the comparison is defined against); --cases parent runs only those.
@@ -21,7 +21,7 @@ One JSON line per case: median / min ms, the yardstick's, their ratio, achieved 
 algorithmic bytes (8 S T read, plus 8 S T where a panel is written) and the library's sha256.
 
     python tools/factor_ols_timing.py [--reps 20] [--out profiles/factor_ols_timing.jsonl] [--append]
-                                      [--other-lib PATH] [--parent-lib PATH] [--cases all|parent]
+                                      [--other-lib PATH] [--parent-lib PATH] [--cases all|parent|other]
 """
 import argparse
 import hashlib
@@ -46,11 +46,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--scale", type=float, default=1.0, help="scale S (a quick look on a busy machine)")
     ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
-    ap.add_argument("--other-lib", default=None, help="another build of the library: the other form of the hot path")
+    ap.add_argument("--other-lib", default=None, help="another build of the library: the same calls in it")
     ap.add_argument("--parent-lib", default=None, help="the parent commit's build: its sts_bp_test as the yardstick")
-    ap.add_argument("--cases", choices=["all", "parent"], default="all")
+    ap.add_argument("--cases", choices=["all", "parent", "other"], default="all")
     a = ap.parse_args()
-    assert a.cases == "all" or a.parent_lib, "--cases parent needs --parent-lib"
+    assert a.cases != "parent" or a.parent_lib, "--cases parent needs --parent-lib"
+    assert a.cases != "other" or a.other_lib, "--cases other needs --other-lib"
     assert a.reps >= 20 or a.scale != 1.0, "at least 20 timed calls per case"
     import torch
     from sparkts import _native
@@ -128,17 +129,19 @@ def main():
                 ("ols_fit_resid_%s_vs_fill" % tag, ols(lib, f, fs, True), fill, "sts_fill(linear)", 2),
                 ("remove_%s" % tag, remove(f, fs), diff, "sts_diff_at_lag", 2),
             ]
-        if a.cases == "parent":
+        if a.cases != "all":
             cases = []
-        if parent:
+        if parent and a.cases != "other":
             cases += [("ols_fit_%s_vs_parent_bp" % tag, ols(lib, f, fs, False), bp(f, fs, parent),
                        "sts_bp_test of parent lib " + parent_hash, 1) for tag, f, fs in (("shared", FS, 0), ("per_series", FP, k * T))]
-        if other and a.cases == "all":
-            cases += [
-                ("ols_fit_shared_vs_other_form", ols(lib, FS, 0, False), ols(other, FS, 0, False), "other lib " + other_hash, 1),
-                ("ols_fit_resid_shared_vs_other_form", ols(lib, FS, 0, True), ols(other, FS, 0, True),
-                 "other lib " + other_hash, 2),
-            ]
+        if other and a.cases != "parent":
+            for tag, f, fs in (("shared", FS, 0), ("per_series", FP, k * T)):
+                cases += [
+                    ("ols_fit_%s_vs_other_form" % tag, ols(lib, f, fs, False), ols(other, f, fs, False),
+                     "other lib " + other_hash, 1),
+                    ("ols_fit_resid_%s_vs_other_form" % tag, ols(lib, f, fs, True), ols(other, f, fs, True),
+                     "other lib " + other_hash, 2),
+                ]
         for name, fn, yard, yname, panels in cases:
             ms, yms = timed_pair(fn, yard, a.reps)
             rec = {"case": name, "S": S, "T": T, "k": k, "reps": a.reps, "ms_median": med(ms), "ms_min": min(ms),

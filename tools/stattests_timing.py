@@ -12,12 +12,16 @@ call by call with the case being measured:
 Breusch-Pagan and Breusch-Godfrey (maxLag 1 and 5) run with k = 3 factors, once shared by the panel
 and once per series.
 
+--other-lib PATH adds the ADF (1, c) and (5, ct), Breusch-Pagan and Breusch-Godfrey cases with the
+same call in ANOTHER build of the library (e.g. the parent commit's) as the yardstick, alternating
+in this one process; --cases other runs only those.
+
 HIP events around every call, every shape warmed up first, --reps timed calls per case (>= 20).
 One JSON line per case: median / min ms, the yardstick's, their ratio, achieved bytes/s
 (8 S T over the median) and the library's sha256.
 
-    python tools/stattests_timing.py [--reps 20] [--cases all|t1t4|bgbp] [--append]
-                                     [--out profiles/stattests_timing.jsonl]
+    python tools/stattests_timing.py [--reps 20] [--cases all|t1t4|bgbp|other] [--append]
+                                     [--out profiles/stattests_timing.jsonl] [--other-lib PATH]
 """
 import argparse
 import hashlib
@@ -37,9 +41,11 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--scale", type=float, default=1.0, help="scale S (a quick look on a busy machine)")
-    ap.add_argument("--cases", choices=["all", "t1t4", "bgbp"], default="all")
+    ap.add_argument("--cases", choices=["all", "t1t4", "bgbp", "other"], default="all")
     ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
+    ap.add_argument("--other-lib", default=None, help="another build of the library: the same calls in it")
     a = ap.parse_args()
+    assert a.cases != "other" or a.other_lib, "--cases other needs --other-lib"
     assert a.reps >= 20 or a.scale != 1.0, "at least 20 timed calls per case"
     import torch
     from sparkts import _native
@@ -47,6 +53,11 @@ def main():
     lib = _native.lib()
     with open(_native.LIB_PATH, "rb") as f:
         lib_hash = hashlib.sha256(f.read()).hexdigest()[:16]
+    other, other_name = None, None
+    if a.other_lib:
+        other = _native.load_variant(a.other_lib)
+        with open(a.other_lib, "rb") as f:
+            other_name = "other lib " + hashlib.sha256(f.read()).hexdigest()[:16]
     sp = torch.cuda.current_stream().cuda_stream
     out = open(a.out, "a" if a.append else "w") if a.out else None
 
@@ -105,8 +116,14 @@ def main():
             ("lb_20_vs_stats", lambda: lib.sts_lb_test(X, S, T, T, K, stat.data_ptr(), pv.data_ptr(), sp), series_stats,
              "sts_series_stats"),
         ]
-        if a.cases == "bgbp":
+        if a.cases in ("bgbp", "other"):
             cases = []
+        if other:
+            def adf(L, p, reg):
+                return lambda: L.sts_adf_test(X, S, T, T, p, reg, stat.data_ptr(), pv.data_ptr(), err.data_ptr(), sp)
+
+            cases += [("adf_1_c_vs_other", adf(lib, 1, REG_C), adf(other, 1, REG_C), other_name),
+                      ("adf_5_ct_vs_other", adf(lib, 5, REG_CT), adf(other, 5, REG_CT), other_name)]
         if a.cases != "t1t4":
             k = 3
             fshared = torch.randn((k, T), dtype=torch.float64, device="cuda")
@@ -119,14 +136,19 @@ def main():
             def adf_5_ct():
                 assert lib.sts_adf_test(X, S, T, T, 5, REG_CT, stat.data_ptr(), pv.data_ptr(), err.data_ptr(), sp) == 0
 
-            def bp(f, fs):
-                return lambda: lib.sts_bp_test(X, S, T, T, f, k, T, fs, stat.data_ptr(), pv.data_ptr(), err.data_ptr(), sp)
+            def bp(f, fs, L=lib):
+                return lambda: L.sts_bp_test(X, S, T, T, f, k, T, fs, stat.data_ptr(), pv.data_ptr(), err.data_ptr(), sp)
 
-            def bg(f, fs, lag):
-                return lambda: lib.sts_bg_test(X, S, T, T, f, k, T, fs, lag, stat.data_ptr(), pv.data_ptr(),
+            def bg(f, fs, lag, L=lib):
+                return lambda: L.sts_bg_test(X, S, T, T, f, k, T, fs, lag, stat.data_ptr(), pv.data_ptr(),
                                                err.data_ptr(), sp)
 
-            cases += [
+            if other:
+                for tag, f, fs in (("shared", FS, 0), ("per_series", FP, k * T)):
+                    cases += [("bp_3_%s_vs_other" % tag, bp(f, fs), bp(f, fs, other), other_name),
+                              ("bg_1_3_%s_vs_other" % tag, bg(f, fs, 1), bg(f, fs, 1, other), other_name),
+                              ("bg_5_3_%s_vs_other" % tag, bg(f, fs, 5), bg(f, fs, 5, other), other_name)]
+            bgbp = [
                 ("bp_3_shared", bp(FS, 0), series_stats, "sts_series_stats"),
                 ("bp_3_shared_vs_dw", bp(FS, 0), dw, "sts_dw_test"),
                 ("bp_3_per_series", bp(FP, k * T), series_stats, "sts_series_stats"),
@@ -139,12 +161,14 @@ def main():
                 ("bg_5_3_per_series", bg(FP, k * T, 5), series_stats, "sts_series_stats"),
                 ("bg_5_3_per_series_vs_adf", bg(FP, k * T, 5), adf_5_ct, "sts_adf_test(5, ct)"),
             ]
+            if a.cases != "other":
+                cases += bgbp
         for name, fn, yard, yname in cases:
             ms, yms = timed_pair(fn, yard, a.reps)
             rec = {"case": name, "S": S, "T": T, "reps": a.reps, "ms_median": med(ms), "ms_min": min(ms),
                    "yardstick": yname, "yard_ms_median": med(yms), "yard_ms_min": min(yms),
                    "ratio_to_yardstick": med(ms) / med(yms), "GBps": 8.0 * S * T / (med(ms) * 1e-3) / 1e9,
-                   "lib_sha256": lib_hash}
+                   "yard_min_to_median": min(yms) / med(yms), "lib_sha256": lib_hash}
             line = json.dumps(rec)
             print(line, flush=True)
             if out:
