@@ -599,8 +599,9 @@ int sts_argarch_fit_host(const double* in, int64_t S, int64_t T, int64_t ld, dou
 
 static int ar_host(decltype(&sts_ar_add) fn, const double* in, double* out, int64_t S, int64_t T, int64_t ld,
                    const double* c, const double* coef, int p) {
-    // not an argument check: p = 0 has no coefficients (coef may be NULL), but the recurrence kernels
-    // still load one per series, so one zero stands in for every series' row (host stride 0)
+    // not an argument check: p = 0 has no coefficients (coef may be NULL) and no kernel loads one; one
+    // zero stands in for every series' row (host stride 0) so that the call keeps its four per-series
+    // arguments and the device call a non-NULL pointer, whatever the caller passed
     const double zero = 0.0;
     const Arg k = p > 0 ? in_vec(coef, p) : in_arg(&zero, sizeof(double), 0);
     return staged(S, T, ld, {in_panel(in), out_panel(out), in_vec(c), k}, [&](const Call& a) {

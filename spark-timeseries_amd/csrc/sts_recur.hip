@@ -67,8 +67,10 @@ struct RecurLane {
         if (OP == kEwmaAdd || OP == kEwmaRemoveInplace || OP == kFillDiffEwma) sm = a.sm[si];
         if (OP == kArAdd || OP == kArRemoveInplace) {
             cc = a.c[si];
+            if (a.p > 0) {   // p = 0 has no coefficients (sts_ar_add / sts_ar_remove accept coef == NULL): nothing to load
 #pragma unroll
-            for (int j = 0; j < H; j++) cf[j] = a.coef[si * a.p + (j < a.p ? j : 0)];
+                for (int j = 0; j < H; j++) cf[j] = a.coef[si * a.p + (j < a.p ? j : 0)];
+            }
         }
     }
     __device__ __forceinline__ void finish(const RecurArgs& a) {

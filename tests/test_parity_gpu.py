@@ -832,6 +832,26 @@ def test_ar_remove_add_bit_exact(torch):
         assert_bits(host(ip), np.array(ref), "remove in place p=%d" % p)
 
 
+@pytest.mark.parametrize("T", [65, 390, 1025])
+def test_ar_effects_order_zero_without_coefficients(torch, T):
+    # p = 0 has no coefficients: sts_ar_add / sts_ar_remove accept coef == NULL and must not load one
+    # (the lane kernels of sts_recur.hip once read coef[0] for the history slot every lane carries)
+    from sparkts import _native
+    L = _native.lib()
+    S = 70
+    x = np.random.default_rng(T).standard_normal((S, T))
+    c = np.linspace(-1.0, 1.0, S)
+    xd, cd = dev(torch, x), dev(torch, c)
+    for name, fn, orc, inplace in (("add", L.sts_ar_add, oracle.ar_add, False), ("add in place", L.sts_ar_add, oracle.ar_add, True),
+                                   ("remove", L.sts_ar_remove, oracle.ar_remove, False),
+                                   ("remove in place", L.sts_ar_remove, oracle.ar_remove, True)):
+        src = xd.clone()
+        out = src if inplace else torch.empty_like(xd)
+        assert fn(src.data_ptr(), out.data_ptr(), S, T, T, T, cd.data_ptr(), None, 0, None) == 0, L.sts_last_error()
+        torch.cuda.synchronize()
+        assert_bits(host(out), np.array([orc(x[s], c[s], []) for s in range(S)]), "%s p=0 T=%d" % (name, T))
+
+
 def test_ar_add_remove_round_trip(torch):
     # T/models/AutoregressionSuite.scala:44-51
     from sparkts.models import ARModel
