@@ -70,6 +70,10 @@ __device__ __forceinline__ void lds_barrier() {
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2v __attribute__((ext_vector_type(2)));   // 16-B lag-matrix stores
 typedef int i4v __attribute__((ext_vector_type(4)));      // 16-B reads of the word-offset tables
+// global address space, spelled out: a pointer that went through an opaque asm is otherwise a
+// generic one, and its accesses flat instructions
+typedef __attribute__((address_space(1))) char gchar;
+typedef __attribute__((address_space(1))) d2v gd2v;
 
 constexpr int kThreads = 256;
 constexpr int kBig = 1 << 30;
@@ -257,7 +261,7 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
     // of a series (which touch its ends) are loaded synchronously with bounds checks
     static_assert(RPT <= 9, "prefetch registers are spelled out for RPT <= 9");
     double2 R0, R1, R2, R3, R4, R5, R6, R7, R8;   // named: an array here ends up in scratch
-    auto interior = [&](int64_t kk) {
+    auto interior = [&](int64_t kk) __attribute__((always_inline)) {
         const int64_t e0 = kk * TW - kHB;
         return e0 >= 0 && e0 + EW <= T && src_al;
     };
@@ -281,6 +285,37 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
         const double2* s2_ = reinterpret_cast<const double2*>(src + ((kk) * TW - kHB));     \
         STS_LD1(0) STS_LD1(1) STS_LD1(2) STS_LD1(3) STS_LD1(4)                              \
         STS_LD1(5) STS_LD1(6) STS_LD1(7) STS_LD1(8)                                         \
+    } while (0)
+// The same loads issued from an interior tile (the row is 16-B aligned): scalar base + 32-bit
+// lane offset, as the interior store pass -- a lane's loads sit 4,096 B apart, one base per two
+// loads (lane offsets tid * 16 and tid * 16 + 4,096), advanced on the scalar unit; the clamp only
+// in the last register, the one that can reach past the extended tile.
+#define STS_LDIN(j)                                                                         \
+    if constexpr (j < RPT) {                                                                \
+        const unsigned o_ = ((j + 1) * kThreads <= NP2) ? ((j & 1) ? lo2_ : lo_) : lc_;     \
+        const gd2v* p_ = (const gd2v*)(lb_[j / 2] + o_);                                    \
+        if constexpr (NT > 0) {                                                             \
+            const d2v v_ = __builtin_nontemporal_load(p_);                                  \
+            R##j = make_double2(v_.x, v_.y);                                                \
+        } else {                                                                            \
+            const d2v v_ = *p_;                                                             \
+            R##j = make_double2(v_.x, v_.y);                                                \
+        }                                                                                   \
+    }
+#define STS_ISSUE_IN(kk)                                                                    \
+    do {                                                                                    \
+        constexpr int LSTR_ = kThreads * 16;                                                \
+        const int tc_ = (NP2 - 1) - (RPT - 1) * kThreads;   /* last lane of the last register */ \
+        unsigned lo_ = (unsigned)tid * 16u, lo2_ = (unsigned)tid * 16u + LSTR_;             \
+        unsigned lc_ = (unsigned)(tid < tc_ ? tid : tc_) * 16u + ((RPT - 1) & 1) * LSTR_;   \
+        asm volatile("" : "+v"(lo_), "+v"(lo2_), "+v"(lc_));                                \
+        const gchar* lb_[(RPT + 1) / 2];                                                    \
+        _Pragma("unroll") for (int m_ = 0; m_ < (RPT + 1) / 2; m_++) {                      \
+            lb_[m_] = (const gchar*)(src + ((kk) * TW - kHB)) + 2 * m_ * LSTR_;             \
+            asm volatile("" : "+s"(lb_[m_]));                                               \
+        }                                                                                   \
+        STS_LDIN(0) STS_LDIN(1) STS_LDIN(2) STS_LDIN(3) STS_LDIN(4)                         \
+        STS_LDIN(5) STS_LDIN(6) STS_LDIN(7) STS_LDIN(8)                                     \
     } while (0)
 // define R on the no-prefetch path too, so the registers are dead between their store to
 // LDS and the next issue (otherwise the loop-carried values stay live across the body).  An
@@ -330,22 +365,26 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
     constexpr int qA0 = kHB;                // E-position of the tile's first step
     constexpr int NTA = NT > 0 ? NT : 1;    // array extent (NT = 0 instantiates no MFMA code)
     constexpr int CPW = TW / 64 / kWaves;   // 64-step chunks per wave
-    auto mid_sums = [&](int p, double y) {
+    auto mid_sums = [&](int p, double y) __attribute__((always_inline)) {
         // sum y / sum y^2 over the series' middle (sts_acf.hpp rule 2): lane l of the chunk
         // at series position p holds y(p + l)
         const double z = acf_mid(p + lane, T) ? y : 0.0;
         acc_s += z;
         acc_q = __builtin_fma(z, z, acc_q);
     };
-    auto mfma_group = [&](auto FROM, auto TO, const double* vb, int64_t kk, int tt0, int tt1) {
+    // (itag: the tile's form, see the tile loop; an interior tile is full and wholly inside the
+    // middle, so it is the unrolled loop alone)
+    auto mfma_group = [&](auto itag, auto FROM, auto TO, const double* vb, int64_t kk, int tt0, int tt1)
+                          __attribute__((always_inline)) {
+        constexpr bool IN = decltype(itag)::value;
         constexpr int F = decltype(FROM)::value, TE = decltype(TO)::value;
         if constexpr (NT > 0 && F < TE) {
             // a tile wholly inside the middle takes the unrolled loop with plain sums; the
             // series' first and last tiles take the per-chunk loop with the per-lane test
-            const bool tile_mid = tt0 >= kAcfEdge && tt1 + kAcfEdge <= T;
+            const bool tile_mid = IN || (tt0 >= kAcfEdge && tt1 + kAcfEdge <= T);
             const int tlen = tt1 - tt0;
             const int nch = (tlen + 63) / 64;
-            const bool full = wave * CPW + CPW <= nch;
+            const bool full = IN || wave * CPW + CPW <= nch;
             int c = wave * CPW + F;
             int cend = wave * CPW + TE;
             if (cend > nch) cend = nch;
@@ -361,7 +400,7 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
                     oa[t] = opq(px(ra));
                     ob[t] = opq(px(rb));
                 }
-                auto chunk_mfma = [&](const double* yb) {
+                auto chunk_mfma = [&](const double* yb) __attribute__((always_inline)) {
                     double av[NTA], bv[NTA];
 #pragma unroll
                     for (int t = 0; t < NT; t++) {
@@ -375,7 +414,8 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
                 };
                 // wave 0 of the first tile also runs chunk -1 (the look-back, y = 0), whose
                 // shifted windows hold the series' first QS t steps
-                if (F == 0 && kk == 0 && wave == 0) chunk_mfma(vb);   // y = 0 there: no middle-sum term
+                if constexpr (!IN)
+                    if (F == 0 && kk == 0 && wave == 0) chunk_mfma(vb);   // y = 0 there: no middle-sum term
                 if (full && tile_mid) {
                     // full chunk range, unrolled: per-lane LDS indices made opaque once per
                     // group (else LICM hoists all of them out of the tile loop and spills),
@@ -406,7 +446,8 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
                     }
                     c = cend;
                 }
-                for (; c < cend; c++) mid_sums(tt0 + 64 * c, chunk_mfma(vb + px(qA0 + 64 * c)));   // chunk start: a multiple of 32
+                if constexpr (!IN)
+                    for (; c < cend; c++) mid_sums(tt0 + 64 * c, chunk_mfma(vb + px(qA0 + 64 * c)));   // chunk start: a multiple of 32
             } else {
                 // U_t += y(j0 + l) x y(j0 + 16t + l)
                 for (; c < cend; c++) {
@@ -422,10 +463,21 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
             }
         }
     };
-    for (int64_t k = k_begin; k < k_end; k++) {
+    // ---- one tile, in two forms.  INTERIOR (IN): a full tile away from the series' ends whose
+    //      extended range was prefetched (e0 >= 0, e0 + EW <= T, the row 16-B aligned) and whose
+    //      output row is null or 16-B aligned -- every bound below is then a constant, the fast
+    //      store pass and the unrolled MFMA loop are the only ones, and nothing of the rare paths
+    //      (edge loads, partial ranges, per-element stores) is in its loop.  GENERAL: any tile,
+    //      with runtime tests.  `have`: the tile's extended range is in the prefetch registers
+    //      (always, for IN); `want_next` (IN only): the next tile is interior too.  Returns whether
+    //      the next tile's loads were issued. ----
+    static_assert(REACH <= kHA && kAcfEdge <= kHB && kAcfEdge <= kHA, "an interior tile needs no end test");
+    auto tile = [&](int64_t k, auto itag, bool have, bool want_next) __attribute__((always_inline)) -> bool {
+        constexpr bool IN = decltype(itag)::value;
         const int t0 = (int)(k * TW);
-        const int t1 = (t0 + TW < T) ? t0 + TW : (int)T;
+        const int t1 = (IN || t0 + TW < T) ? t0 + TW : (int)T;
         const int e0 = t0 - kHB;
+        if constexpr (IN) have = true;
 
         // ---- 1. prefetched registers (or a bounds-checked edge load) -> LDS; for prefetched
         //      tiles the validity ballots come straight from the registers: register j of
@@ -464,7 +516,7 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
                 vals[px(q)] = (t >= 0 && t < T) ? src[t] : __builtin_nan("");
             }
         }
-        const bool have_next = (k + 1 < k_end) && interior(k + 1);
+        const bool have_next = IN ? want_next : (k + 1 < k_end) && interior(k + 1);
         STAMP(0);
         lds_barrier();
         STAMP(1);
@@ -473,7 +525,7 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
         const int qA = kHB;
         const int qW = kHB + (t1 - t0);                  // end of the written range
         int qB = qW + REACH;
-        if (e0 + qB > T) qB = (int)T - e0;
+        if (!IN && e0 + qB > T) qB = (int)T - e0;
 
         // ---- 2. validity ballots from LDS for the edge tiles (wave v owns words v, v+4, ...) ----
         if (!have) {
@@ -514,7 +566,7 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
             const int f0 = (w0 < NW && m0) ? w0 * 64 + __ffsll(m0) - 1 : kBig;
             const int f1 = (w1 < NW && m1) ? w1 * 64 + __ffsll(m1) - 1 : kBig;
             // NaN positions to impute: invalid AND inside [qA, qB)
-            auto need = [&](int w, unsigned long long m) -> unsigned long long {
+            auto need = [&](int w, unsigned long long m) __attribute__((always_inline)) -> unsigned long long {
                 const int lo = qA - w * 64, hi = qB - w * 64;      // bit range [lo, hi)
                 if (method == STS_FILL_NONE || hi <= 0 || lo >= 64) return 0ull;
                 unsigned long long r = ~m;
@@ -560,7 +612,7 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
             // slow paths: a NaN run longer than the halos (rare); the answers are cached for
             // the next tiles of this workgroup, so a long gap is scanned once per workgroup
             int lext = -1, next = (int)T;
-            if (needL && e0 > 0 && firstValidE > qA && nnan > 0)
+            if (needL && (IN || e0 > 0) && firstValidE > qA && nnan > 0)
                 lext = (sh_c[0] == e0) ? sh_c[1] : (int)scan_back(src, e0, lane);
             if (needN && e0 + EW < T && qB > qA && lastValidE < qB - 1 && nnan > 0) {
                 const int from = e0 + EW;
@@ -613,7 +665,7 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
             const double lextv = sh_d[1], nextv = sh_d[2];
             // two versions of the loop: only a tile flagged by the word scan carries the
             // long-run chain code
-            auto impute = [&](auto long_tag) {
+            auto impute = [&](auto long_tag) __attribute__((always_inline)) {
             constexpr bool LONG = decltype(long_tag)::value;
             for (int idx = tid; idx < nnan; idx += kThreads) {
                 // the word holding NaN #idx: last w with wbase[w] <= idx.  The offsets never
@@ -743,15 +795,81 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
             // [kHB, kHB + TW) and every y the MFMA phase reads is F - c0 (no zero tail), so
             // every index and guard below is a compile-time constant
             const bool fast = (dst == nullptr || al) && (t1 - t0 == TW) && (NT == 0 || e0 + qW + REACH <= T);
-            if (fast) {
+            if constexpr (IN) {
+                // interior form: the fast path below with no runtime guard.  The stores take the
+                // scalar-base form (SGPR pair + 32-bit lane offset): a lane's stores sit kThreads *
+                // 16 = 4,096 B apart, one past the 13-bit immediate, so one base serves two stores
+                // (lane offsets tid * 16 and tid * 16 + 4,096: two accesses sharing base, lane
+                // offset and differing only in the immediate share a 64-bit per-lane address
+                // instead) and the next base is two scalar adds away -- no per-store 64-bit vector
+                // add.  Each base is opaque, else the adds are folded back into per-lane addresses.
+                // A null `dst` picks the pass without stores.
+                auto pass = [&](auto wtag) __attribute__((always_inline)) {
+                    constexpr bool WR = decltype(wtag)::value;
+                    constexpr int FS = TW / 2 / kThreads;                          // stored double2
+                    constexpr int FY = NT > 0 ? (NP2 - kHB / 2 + kThreads - 1) / kThreads : FS;
+                    constexpr int FH = (FY + 1) / 2;     // two halves: fewer live registers
+                    constexpr int SSTR = kThreads * 16;  // bytes between a lane's consecutive stores
+                    const int pvq = opq(px2((kHB >> 1) + tid));   // px2(vq + jj kThreads) = pvq + jj PX2S
+                    unsigned dpo = (unsigned)tid * 16u;
+                    unsigned dpo2 = (unsigned)tid * 16u + SSTR;
+                    asm volatile("" : "+v"(dpo), "+v"(dpo2));   // per tile: else LICM keeps dst + dpo as a 64-bit VGPR pair
+                    // the last register's read is clamped, not predicated: a branch between the
+                    // stores would end the block the scalar-base form is matched in
+                    constexpr int VL = NP2 - kHB / 2 - (FY - 1) * kThreads;   // its lanes [0, VL)
+                    const int pvl = opq(px2((kHB >> 1) + (tid < VL ? tid : VL - 1)));
+                    gchar* sb[(FS + 1) / 2];
+                    if constexpr (WR) {
+#pragma unroll
+                        for (int m = 0; m < (FS + 1) / 2; m++) {
+                            sb[m] = (gchar*)(dst + t0) + 2 * m * SSTR;
+                            asm volatile("" : "+s"(sb[m]));
+                        }
+                    }
+#pragma unroll
+                    for (int h = 0; h < 2; h++) {
+                        double2 fv[FH];
+#pragma unroll
+                        for (int j = 0; j < FH; j++) {
+                            const int jj = h * FH + j;
+                            if (jj < FY) fv[j] = v2[(jj * kThreads + kThreads <= NP2 - kHB / 2 ? pvq : pvl) + jj * PX2S];
+                        }
+#pragma unroll
+                        for (int j = 0; j < FH; j++) {
+                            const int jj = h * FH + j;
+                            if (jj >= FY) continue;
+                            if constexpr (WR) {
+                                if (jj < FS) {   // non-temporal: A/B on C3 +1 %
+                                    gchar* dq = sb[jj / 2] + ((jj & 1) ? dpo2 : dpo);
+                                    __builtin_nontemporal_store(d2v{fv[j].x, fv[j].y}, (gd2v*)dq);
+                                }
+                            }
+                            // (the range test only in the one register that can fail it)
+                            if (NT > 0 && (jj * kThreads + kThreads <= NP2 - kHB / 2 ||
+                                           tid + jj * kThreads < NP2 - kHB / 2)) {
+                                double2 y;
+                                y.x = fv[j].x - c0;
+                                y.y = fv[j].y - c0;
+                                v2[pvq + jj * PX2S] = y;
+                            }
+                        }
+                    }
+                };
+                if (dst != nullptr) pass(std::true_type{});
+                else pass(std::false_type{});
+            } else if (fast) {
                 constexpr int FS = TW / 2 / kThreads;                          // stored double2
                 constexpr int FY = NT > 0 ? (NP2 - kHB / 2 + kThreads - 1) / kThreads : FS;
                 constexpr int FH = (FY + 1) / 2;     // two halves: fewer live registers
                 const int vq = (kHB >> 1) + tid;
                 const int pvq = opq(px2(vq));   // px2(vq + jj kThreads) = pvq + jj PX2S
                 const bool wr = dst != nullptr;   // wave-uniform (a null test of dp is per lane)
-                // uniform tile base (SGPRs) + a 32-bit lane offset: the saddr store form, no
-                // 64-bit per-lane pointer kept live across the tile loop
+                // uniform tile base + a 32-bit lane offset, so that no 64-bit per-lane pointer is
+                // kept live across the tile loop.  (The stores do NOT come out in the scalar-base
+                // form here: a lane's stores sit 4,096 B apart, one past the immediate range, and
+                // the compiler forms a 64-bit vector address per store.  Only the series' first
+                // and last tiles and unaligned rows take this path; the interior form above
+                // spells the scalar bases out.)
                 char* const dpb = reinterpret_cast<char*>(dst + t0);
                 unsigned dpo = (unsigned)tid * 16u;
                 asm volatile("" : "+v"(dpo));   // per tile: else LICM keeps dst + dpo as a 64-bit VGPR pair
@@ -807,10 +925,14 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
             }
             // shifted scheme, first tile: the pre-chunk (positions [0, 4t) of the series) reads
             // the look-back range as y = 0
-            if (SHIFTED && NT > 0 && e0 < 0 && tid < kHB / 2) v2[px2(tid)] = make_double2(0.0, 0.0);
+            if (!IN && SHIFTED && NT > 0 && e0 < 0 && tid < kHB / 2) v2[px2(tid)] = make_double2(0.0, 0.0);
         }
-        if (have_next) STS_ISSUE(k + 1);   // in flight during the MFMA phase of tile k
-        else STS_CLEAR();
+        if (have_next) {   // in flight during the MFMA phase of tile k
+            if constexpr (IN) STS_ISSUE_IN(k + 1);
+            else STS_ISSUE(k + 1);
+        } else {
+            STS_CLEAR();
+        }
         // lag matrix (fill only; S/Lag.scala:62-77): column c - init holds x[r + max_lag - c] at
         // row r.  Each column's rows of this tile go out as 16-B pairs aligned on the column's
         // own address (one wave instruction = 1 KB of one column; round 3 stored the two halves
@@ -849,16 +971,41 @@ __global__ __launch_bounds__(NTH, STS_TILE_WGS) void tile_kernel(TileArgs a) {
             //      STS_FILL_PRIO, so a SIMD's arbiter favours the waves of workgroups in their fill
             //      and store phases (memory issue) over the MFMA stream of the others ----
             __builtin_amdgcn_s_setprio(0);
-            mfma_group(std::integral_constant<int, 0>{}, std::integral_constant<int, CPW>{}, vals, k, t0, t1);
+            mfma_group(itag, std::integral_constant<int, 0>{}, std::integral_constant<int, CPW>{}, vals, k, t0, t1);
             __builtin_amdgcn_s_setprio(STS_FILL_PRIO);
         }
-        have = have_next;
         STAMP(10);
         lds_barrier();   // vals / mask / lists are reused by the next tile
         STAMP(11);
+        return have_next;
+    };
+    // ---- the chunk's tiles: the interior ones are consecutive, [ki0, ki1) (tile 0 is never
+    //      interior, and at most the series' last two tiles fail the end test), found once per
+    //      chunk; they run in a loop of the interior form alone, the others in the general form ----
+    // (tile numbers as int here: t0 = k TW is one; 32-bit scalar loop tests)
+    const int kb = (int)k_begin, ke = (int)k_end;
+    int ki0 = kb, ki1 = kb;
+    if (src_al && (dst == nullptr || (reinterpret_cast<uintptr_t>(dst) & 15) == 0)) {
+        ki0 = kb > 0 ? kb : 1;
+        ki1 = ke > ki0 ? ke : ki0;
+        while (ki1 > ki0 && !interior(ki1 - 1)) ki1--;
     }
+    // (three stretches in sequence, not one loop choosing a form per tile: what the compiler hoists
+    // out of one form's loop is then not live across the other's)
+    int k = kb;
+    if (k < ki0) have = tile(k++, std::false_type{}, have, false);   // tile 0 of the series
+    if (k < ki1) {
+        do {
+            tile(k, std::true_type{}, true, k + 1 < ki1);
+            k++;
+        } while (k < ki1);
+        have = false;   // the tile after the last interior one was not prefetched
+    }
+    for (; k < ke; k++) have = tile(k, std::false_type{}, have, false);
 #undef STS_ISSUE
 #undef STS_LD1
+#undef STS_ISSUE_IN
+#undef STS_LDIN
 #undef STS_ST1
 #undef STS_CLEAR
     if (series_err && a.err) a.err[s] = STS_ERR_ALL_NAN;
