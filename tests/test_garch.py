@@ -4,12 +4,14 @@ CPU (no GPU):
 * the oracle against the reference's own GARCHSuite (T/models/GARCHSuite.scala), on inputs
   regenerated with the commons-math3 MersenneTwister restatement;
 * fdlibm's log (StrictMath.log, used by oracle and device) within 1 ulp of math.log;
-* the device optimizer state machine (csrc/sts_garch_opt.hpp compiled for the host) against
-  the oracle's straight-line restatement: status, parameter bits, evaluation count.
+* the device optimizer state machine (csrc/sts_garch_opt.hpp compiled for the host) against the oracle's straight-line restatement: status, parameter bits,
+  evaluation count; and its complete output, passes over the series included, against the
+  recorded tests/golden/cg_paths.json.
 GPU: the HIP path through the C ABI against the oracle -- logLikelihood / gradient, the
 fitted parameters and the remove / add effects bit-exact; ARGARCH's AR stage within 1e-10
 (the Householder-QR bar of a11) and its GARCH stage bit-exact given the residuals.
 """
+import json
 import math
 import os
 import shutil
@@ -23,6 +25,7 @@ from mt19937 import MersenneTwister
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HARNESS = os.path.join(ROOT, "tests", "native", "garch_sm_harness.cpp")
+PATHS = os.path.join(ROOT, "tests", "golden", "cg_paths.json")
 RTOL = 1e-10
 
 
@@ -122,28 +125,37 @@ def harness(tmp_path_factory):
     gxx = shutil.which("g++")
     if gxx is None:
         pytest.skip("g++ not available")
-    oracle.lib()
     out = str(tmp_path_factory.mktemp("garch") / "garch_sm")
+    build_harness(gxx, out)
+    return out
+
+
+def build_harness(gxx, out):
+    oracle.lib()
     lib_dir = os.path.join(ROOT, "oracle", "_build")
     subprocess.check_call([gxx, "-O2", "-std=c++17", "-ffp-contract=off",
                            "-I", os.path.join(ROOT, "include"),
                            "-I", os.path.join(ROOT, "spark-timeseries_amd", "csrc"),
                            HARNESS, "-L", lib_dir, "-lsts_oracle", "-Wl,-rpath," + lib_dir, "-o", out])
-    return out
+
+
+def harness_lines(harness, x):
+    """the harness's output, one line per series: status, three parameter bits, evaluations, passes"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    inp = "%d %d\n" % x.shape + " ".join("%x" % v for v in x.view(np.uint64).ravel())
+    return subprocess.run([harness], input=inp, capture_output=True, text=True, check=True).stdout.splitlines()
 
 
 def run_harness(harness, x):
-    x = np.ascontiguousarray(x, dtype=np.float64)
-    inp = "%d %d\n" % x.shape + " ".join("%x" % v for v in x.view(np.uint64).ravel())
-    out = subprocess.run([harness], input=inp, capture_output=True, text=True, check=True).stdout.split()
-    rows = np.array(out, dtype=object).reshape(-1, 6)
+    """-> status, parameters, evaluations, passes over the series, one entry per row of x"""
+    rows = np.array([l.split() for l in harness_lines(harness, x)], dtype=object).reshape(-1, 6)
     st = rows[:, 0].astype(int)
     par = np.array([[int(b, 16) for b in r] for r in rows[:, 1:4]], dtype=np.uint64).view(np.float64)
-    return st, par, rows[:, 4].astype(int)
+    return st, par, rows[:, 4].astype(int), rows[:, 5].astype(int)
 
 
 def check_machine(harness, x):
-    st, par, ev = run_harness(harness, x)
+    st, par, ev, _ = run_harness(harness, x)
     for i in range(x.shape[0]):
         rst, rpar, rev = oracle.garch_fit(x[i])
         assert st[i] == rst, (i, st[i], rst)
@@ -160,15 +172,37 @@ def test_state_machine_matches_oracle(harness):
     check_machine(harness, garch_panel(1, 20, 288))
 
 
-def test_state_machine_edge_series(harness):
+def edge_panel():
     x = garch_panel(6, 40, 7)
     x[1, 17] = np.nan                 # NaN: TooManyEvaluations after 10000 evaluations
     x[2] = 0.0                        # constant zero
     x[3] = 1.5                        # constant
     x[4, ::2] *= 50                   # heavy tails
-    check_machine(harness, x)
+    return x
+
+
+def test_state_machine_edge_series(harness):
+    check_machine(harness, edge_panel())
     check_machine(harness, FIT2[None, :])
     check_machine(harness, np.array([[0.3]]))      # n = 1: the initial guess converges
+
+
+def path_cases():
+    """name -> panel: the inputs whose complete harness lines tests/golden/cg_paths.json records"""
+    return {"panel_12x600_seed100": garch_panel(12, 600, 100), "panel_4x12_seed0": garch_panel(4, 12, 0),
+            "panel_1x20_seed288": garch_panel(1, 20, 288), "edge_panel": edge_panel(), "fit2": FIT2[None, :],
+            "single_value": np.array([[0.3]])}
+
+
+def test_optimizer_paths_are_the_recorded_ones(harness):
+    """Status, point bits, evaluations AND passes, character for character: the passes are what
+    the evaluation cache decides and what the device time follows."""
+    with open(PATHS) as f:
+        golden = json.load(f)["garch"]
+    cases = path_cases()
+    assert sorted(golden) == sorted(cases)
+    for name, x in cases.items():
+        assert harness_lines(harness, x) == golden[name], name
 
 
 # ---------------- GPU: HIP path vs oracle ----------------
